@@ -55,6 +55,31 @@ the communication + decompression + update that the backward did not hide.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch-size B]
        [--compressor gaussian] [--density 0.001] [--model resnet50]
+       [--full] [--dump-outputs DIR]
+
+A plain run does only what the headline figure needs: set-up, W warm-up steps,
+the K timed steps of the headline phase, then the one JSON line.  Everything
+else described above and below -- the bf16 / fp32-MFMA / dense / reference-batch
+/ further-model phases, the fabric probe and the replica digest -- runs only
+with ``--full`` (their ``--no-*-phase`` switches select among them there).
+
+``--dump-outputs DIR`` writes, after the timed steps, what the timed path
+leaves its caller: ``DIR/loss.npy`` (float64) and the fp32 ``weights`` /
+``momentum`` or ``velocity`` (DGC momentum correction) / ``residuals`` arenas
+of the optimizer as ``DIR/<name>.npy`` (float32).  An arena of more than
+``DUMP_MAX_ELEMS`` elements is written as a fixed, seeded sample of that many
+(the same positions in every run).  The step that is dumped is one more,
+untimed call of the very step callable the loop timed, made after the timed
+steps from IDENTICAL inputs: the training state is first put back to what it
+was before the warm-up (seeded initial weights, zero residuals / velocity /
+momentum; ``snapshot_state`` / ``restore_state``), the batch is the seeded one
+next in turn.  The state the timed steps themselves end in is not comparable:
+the grad-weight GEMMs sum with float atomics, so gradients differ in their
+last bits from run to run, and the compressor's threshold turns such a bit
+into a sent-or-kept entry, which the following steps amplify (measured after
+25 steps: weights 1e-3, velocity as large as its own maximum).  One step from
+the same state differs by summation rounding only, so two builds can be
+compared output for output.
 
 N > 1: after the timed loop every rank digests its fp32 weight arena (fp64
 sum + 64-bit content hash, one HIP reduction) and the digests are all-gathered:
@@ -72,9 +97,15 @@ import time
 from typing import Optional
 
 # MIOpen tuning state lives in the repo so a fresh box reuses the convolution
-# solutions found once by `bench.py --cudnn-benchmark` (tuning/miopen/*.udb).
+# solutions found once by `bench.py --cudnn-benchmark` (tuning/miopen/*.udb);
+# MIOpen rewrites its database as it runs, so it gets an untracked working copy
+# of the committed files (tuning/miopen_db.py), not the files themselves.
 _HERE = os.path.dirname(os.path.abspath(__file__))
-os.environ.setdefault("MIOPEN_USER_DB_PATH", os.path.join(_HERE, "tuning", "miopen"))
+if "MIOPEN_USER_DB_PATH" not in os.environ:
+    if _HERE not in sys.path:
+        sys.path.insert(0, _HERE)
+    from tuning.miopen_db import user_db_path
+    os.environ["MIOPEN_USER_DB_PATH"] = user_db_path()
 os.makedirs(os.environ["MIOPEN_USER_DB_PATH"], exist_ok=True)
 
 import torch  # noqa: E402
@@ -163,7 +194,105 @@ def parse():
                          "(same precision / compressor / density); 'none' skips them")
     ap.add_argument("--model-steps", type=int, default=10, help="timed steps of each further model phase")
     ap.add_argument("--json-out", default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline phase: the bf16 / fp32-MFMA / dense / "
+                         "reference-batch / further-model phases, the fabric probe and the replica digest")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps run the timed step once more, untimed, from the seeded initial state "
+                         "and write what it computed (loss, weights, momentum / velocity, residuals) as "
+                         "DIR/<name>.npy: the same from run to run up to summation rounding")
     return ap.parse_args()
+
+
+# --dump-outputs: largest array written whole; a larger one is sampled at this
+# many fixed positions (at most 4 fp32 arenas of 3 M elements: 48 MB in all)
+DUMP_MAX_ELEMS = 3_000_000
+DUMP_SEED = 20240229
+
+
+def dump_sample(t: torch.Tensor, max_elems: int = DUMP_MAX_ELEMS) -> torch.Tensor:
+    """``t`` flattened, or -- above ``max_elems`` elements -- its values at
+    ``max_elems`` sorted positions drawn once from a seeded host generator: a
+    pure function of (numel, max_elems), identical in every run and build."""
+    t = t.detach().reshape(-1)
+    if t.numel() <= max_elems:
+        return t
+    g = torch.Generator(device="cpu")
+    g.manual_seed(DUMP_SEED)
+    idx = torch.randint(0, t.numel(), (max_elems,), generator=g).sort().values
+    return t[idx.to(t.device)]
+
+
+_STATE_ARENAS = ("weights", "momentum", "velocity", "residuals")
+
+
+def snapshot_state(ph: "Phase") -> dict:
+    """Copies of the phase's training state before its first step: the
+    optimizer's arenas that exist already and the model's buffers (BatchNorm
+    running statistics).  Only taken for --dump-outputs."""
+    arena = ph.opt.arena
+    snap = {"arenas": {}, "buffers": {}}
+    for name in _STATE_ARENAS:
+        t = getattr(arena, name, None)
+        if t is not None:
+            snap["arenas"][name] = t.detach().clone()
+    for k, b in ph.trainer.net.named_buffers():
+        snap["buffers"][k] = b.detach().clone()
+    return snap
+
+
+def restore_state(ph: "Phase", snap: dict) -> None:
+    """Put the training state back, in place (parameters are views of the
+    weight arena; a captured graph keeps its addresses): arenas and buffers
+    from the snapshot, an arena created since (the momentum of plain momentum
+    SGD, born at the first step) to zero, the bf16 shadow weights re-cast."""
+    arena = ph.opt.arena
+    with torch.no_grad():
+        for name in _STATE_ARENAS:
+            t = getattr(arena, name, None)
+            if t is None:
+                continue
+            if name in snap["arenas"]:
+                t.copy_(snap["arenas"][name])
+            else:
+                t.zero_()
+        for k, b in ph.trainer.net.named_buffers():
+            if k in snap["buffers"]:
+                b.copy_(snap["buffers"][k])
+    if hasattr(ph.opt, "refresh_shadow"):
+        ph.opt.refresh_shadow()
+    if ph.state is not None:
+        ph.state["hidden"] = None      # LSTM: the carried hidden state starts anew
+
+
+def dump_step(ph: "Phase", snap: dict) -> float:
+    """One untimed call of the phase's step callable from the restored state;
+    returns its loss.  Every rank makes the call (its collectives)."""
+    torch.cuda.synchronize()
+    restore_state(ph, snap)
+    ph.step()
+    torch.cuda.synchronize()
+    return ph.trainer.current_loss()
+
+
+def dump_outputs(dirpath: str, ph: "Phase", loss: float) -> dict:
+    """Write the outputs of the phase's last step as ``dirpath/<name>.npy``
+    (float64 loss, float32 arenas); returns {name: elements written}."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    arena = ph.opt.arena
+    arrays = {"loss": torch.tensor([loss], dtype=torch.float64)}
+    # momentum: plain momentum SGD; velocity: DGC momentum correction (one of the two exists)
+    for name in _STATE_ARENAS:
+        t = getattr(arena, name, None)
+        if t is not None:
+            arrays[name] = dump_sample(t).to(torch.float32)
+    written = {}
+    for name, t in arrays.items():
+        a = t.cpu().numpy()
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+        written[name] = int(a.size)
+    return written
 
 
 def probe_collectives(ex, P: int, dev, rec_bytes: int, dense_bytes: int, iters: int = 10):
@@ -231,6 +360,7 @@ class Phase:
         self.trainer, self.opt, self.comp_name, self.is_sparse, self.batch = trainer, opt, comp_name, is_sparse, batch
         self.model = model
         self.step = None
+        self.state = None      # run_phase: what the step callable carries between calls (LSTM hidden state)
 
 
 def build(args, amp: str, dense: bool, threshold: int, P: int, rank: int, batch: int,
@@ -283,7 +413,7 @@ def run_phase(args, ph: Phase, steps: int, warmup: int, P: int, graph: Optional[
     from gaussiank_sgd_amd.parallel import comm
 
     trainer, opt = ph.trainer, ph.opt
-    state = {"hidden": None}
+    state = ph.state = {"hidden": None}
     lstm = ph.model == "lstm"
     clip = 0.25 if lstm else None  # reference dist_trainer.py:80-85
     marks = []   # (end of backward, end of update) event pairs of the timed steps
@@ -558,6 +688,7 @@ def main() -> int:
     ph = build(args, amp, args.dense, args.threshold, P, rank, args.batch_size)
     trainer, opt, comp_name, is_sparse = ph.trainer, ph.opt, ph.comp_name, ph.is_sparse
     nparams = sum(p.numel() for p in trainer.net.parameters() if p.requires_grad)
+    snap = snapshot_state(ph) if args.dump_outputs else None
     elapsed, exposed = run_phase(args, ph, args.steps, args.warmup, P)
     loss = trainer.current_loss()
     pairs = opt._collect_selected(with_totals=True)
@@ -573,7 +704,7 @@ def main() -> int:
     kind = opt._exchanger.kind if opt._exchanger is not None else "none"
     phases = {"headline": phase_info(ph)}
     replicas = None
-    if P > 1:
+    if P > 1 and args.full:
         # bit-identical replicas: all-gather a digest of every rank's weight arena
         torch.cuda.synchronize()
         d = ops.arena_digest(opt.arena.weights)
@@ -582,6 +713,13 @@ def main() -> int:
         allv = [torch.zeros_like(mine) for _ in range(P)]
         torch.distributed.all_gather(allv, mine)
         replicas = all(torch.equal(allv[0], v) for v in allv[1:])
+    dumped = None
+    if snap is not None:
+        # everything above describes the timed steps; now the one untimed step from the restored state
+        dump_loss = dump_step(ph, snap)
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, ph, dump_loss)
+        del snap
     ms = elapsed / args.steps * 1e3
     imgs = P * args.batch_size * tok_per_sample * args.steps / elapsed
     metric = METRIC if args.model == "resnet50" else "%s (whole node) %s k=%g%% on MI355X" % (
@@ -634,6 +772,8 @@ def main() -> int:
         "selected_over_k": round(sent / k_total, 4) if is_sparse and k_total else None,
         "params": nparams,
         "final_loss": round(loss, 4) if loss == loss else None,
+        "full": bool(args.full),
+        "dumped_outputs": dumped,
         "phases": phases,
     }
     del trainer, opt   # the Phase holder keeps the only references; release() drops them
@@ -660,8 +800,9 @@ def main() -> int:
                         P, torch.cuda.get_device_name(), ex.kind, col[op]["points_bytes_us"])},
                     key=str(P))
 
-    alive = True
-    if P > 1 and os.environ.get("GKSGD_BENCH_PROBE", "1") == "1":
+    # a plain run ends with the headline: every secondary phase below needs --full
+    alive = bool(args.full)
+    if alive and P > 1 and os.environ.get("GKSGD_BENCH_PROBE", "1") == "1":
         alive = optional_phase("collectives", out, P, collectives_probe)
     release(ph)
     ph = None

@@ -15,7 +15,9 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 _HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-os.environ.setdefault("MIOPEN_USER_DB_PATH", os.path.join(_HERE, "tuning", "miopen"))
+if "MIOPEN_USER_DB_PATH" not in os.environ:
+    from tuning.miopen_db import user_db_path  # noqa: E402  (untracked working copy of tuning/miopen)
+    os.environ["MIOPEN_USER_DB_PATH"] = user_db_path()
 
 import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402

@@ -41,6 +41,95 @@ def test_reference_batches_and_bert_buckets(bench):
     assert bench.DEFAULT_THRESHOLD["bert"] * 4 == pytest.approx(26e6, rel=0.1)
 
 
+def test_plain_run_is_the_default_and_full_is_opt_in(bench, monkeypatch):
+    import sys
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_sample_is_whole_below_the_cap_and_a_fixed_sample_above(bench):
+    import torch
+    t = torch.arange(1000, dtype=torch.float32)
+    assert torch.equal(bench.dump_sample(t.view(10, 100), max_elems=1000), t)      # whole, flattened
+    s1 = bench.dump_sample(t, max_elems=64)
+    s2 = bench.dump_sample(t.clone(), max_elems=64)
+    assert s1.numel() == 64 and torch.equal(s1, s2)                                # same positions every time
+    assert torch.equal(s1, s1.sort().values) and 0 <= s1.min() and s1.max() < 1000  # values are the positions here
+    assert s1.unique().numel() > 32                                                # spread, not one spot
+    # all --dump-outputs arrays together stay below 64 MB
+    assert 4 * bench.DUMP_MAX_ELEMS * 4 + 8 <= 64 * 10 ** 6
+
+
+def test_dump_outputs_writes_float_npy(bench, tmp_path):
+    import types
+    import numpy as np
+    import torch
+    arena = types.SimpleNamespace(weights=torch.arange(6, dtype=torch.float32), momentum=None,
+                                  residuals=torch.ones(6))
+    ph = types.SimpleNamespace(opt=types.SimpleNamespace(arena=arena))
+    written = bench.dump_outputs(str(tmp_path / "o"), ph, 2.5)
+    assert written == {"loss": 1, "weights": 6, "residuals": 6}        # no momentum arena: no file
+    assert sorted(p.name for p in (tmp_path / "o").iterdir()) == ["loss.npy", "residuals.npy", "weights.npy"]
+    loss, w = np.load(tmp_path / "o" / "loss.npy"), np.load(tmp_path / "o" / "weights.npy")
+    assert loss.dtype == np.float64 and loss.tolist() == [2.5]
+    assert w.dtype == np.float32 and w.tolist() == [0, 1, 2, 3, 4, 5]
+
+
+def test_snapshot_and_restore_state_put_the_training_state_back_in_place(bench):
+    """The dump step starts from the state before the warm-up: arenas and
+    buffers restored in place, an arena born later zeroed, LSTM hidden state dropped."""
+    import types
+    import torch
+    net = torch.nn.BatchNorm1d(3)
+    arena = types.SimpleNamespace(weights=torch.arange(4.0), residuals=torch.zeros(4), velocity=torch.zeros(4),
+                                  momentum=None)
+    refreshed = []
+    opt = types.SimpleNamespace(arena=arena, refresh_shadow=lambda: refreshed.append(1))
+    ph = types.SimpleNamespace(opt=opt, trainer=types.SimpleNamespace(net=net), state={"hidden": "h"})
+    snap = bench.snapshot_state(ph)
+    assert sorted(snap["arenas"]) == ["residuals", "velocity", "weights"] and "running_mean" in snap["buffers"]
+    w_ptr = arena.weights.data_ptr()
+    arena.weights += 1.0
+    arena.residuals += 2.0
+    arena.velocity += 3.0
+    arena.momentum = torch.ones(4)          # created by the first step
+    net.running_mean += 5.0
+    bench.restore_state(ph, snap)
+    assert arena.weights.data_ptr() == w_ptr and arena.weights.tolist() == [0, 1, 2, 3]
+    assert not arena.residuals.any() and not arena.velocity.any() and not arena.momentum.any()
+    assert not net.running_mean.any() and refreshed == [1] and ph.state["hidden"] is None
+
+
+def test_miopen_user_db_is_a_working_copy_with_fallbacks(bench, tmp_path, monkeypatch):
+    """MIOpen gets a copy of tuning/miopen, not the tracked files; where the
+    checkout's own build/ cannot be written the copy goes to the temporary
+    directory, and failing that the committed directory is used read-only."""
+    from tuning import miopen_db
+    committed = sorted(os.listdir(miopen_db.COMMITTED))
+    assert committed and os.path.dirname(miopen_db.WORKING) == os.path.join(ROOT, "build")
+    w = miopen_db.user_db_path(str(tmp_path / "w"))
+    assert w == str(tmp_path / "w") and sorted(os.listdir(w)) == committed
+    # what MIOpen wrote since is kept
+    first = os.path.join(w, committed[0])
+    with open(first, "a") as f:
+        f.write("learnt\n")
+    miopen_db.user_db_path(w)
+    assert open(first).read().endswith("learnt\n")
+    # unusable working directory (its parent is a file): per-user copy under the temporary directory
+    blocker = tmp_path / "file"
+    blocker.write_text("x")
+    monkeypatch.setattr(miopen_db.tempfile, "tempdir", str(tmp_path / "tmp"))
+    t = miopen_db.user_db_path(str(blocker / "db"))
+    assert t.startswith(str(tmp_path / "tmp")) and sorted(os.listdir(t)) == committed
+    # neither can be written: the committed directory itself
+    monkeypatch.setattr(miopen_db, "_fallback", lambda: str(blocker / "other"))
+    assert miopen_db.user_db_path(str(blocker / "db")) == miopen_db.COMMITTED
+
+
 def test_bert_default_threshold_gives_buckets(bench):
     """The BERT default threshold splits the 110 M gradients into >= 4 buckets
     (reference grouping rule: reverse registration order until >= threshold)."""

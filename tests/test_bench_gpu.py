@@ -30,7 +30,9 @@ def _free_port():
     return p
 
 
-def _bench(*extra, gpus=2, timeout=480, probe=False, env_extra=None, native=False):
+def _bench(*extra, gpus=2, timeout=480, probe=False, env_extra=None, native=False, full=True):
+    """One bench.py run.  full: with ``--full`` (the secondary phases, the
+    fabric probe and the replica digest these tests assert on)."""
     env = dict(os.environ, GKSGD_DIST_BACKEND="gloo", MASTER_PORT=str(_free_port()), HSA_ENABLE_IPC_MODE_LEGACY="0",
                GKSGD_BENCH_PROBE="1" if probe else "0")
     env.update(env_extra or {})
@@ -38,7 +40,7 @@ def _bench(*extra, gpus=2, timeout=480, probe=False, env_extra=None, native=Fals
     env.pop("RANK", None)
     env.pop("LOCAL_RANK", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus)] + \
-        ([] if native else ["--no-native-rccl"]) + list(extra)
+        ([] if native else ["--no-native-rccl"]) + (["--full"] if full else []) + list(extra)
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
     assert p.returncode == 0, "bench.py failed (%d):\n%s\n%s" % (p.returncode, p.stdout[-3000:], p.stderr[-3000:])
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -77,6 +79,69 @@ def test_bench_resnet50_two_ranks_one_gpu(cuda):
     assert all(p["exchange"] == "torch" for p in ph.values())
     assert ph["ref_bs8"]["per_gpu_batch"] == 8 and ph["dense"]["buckets"] > 1
     assert not [k for k in out if k.endswith("_error")]
+
+
+_PLAIN = ("--model", "resnet20", "--steps", "3", "--warmup", "1", "--batch-size", "32")
+_DUMPED = ("weights", "velocity", "residuals")
+
+
+@pytest.fixture(scope="module")
+def plain_runs(cuda, tmp_path_factory):
+    """Two plain (no ``--full``) runs with the same arguments and ``--dump-outputs``."""
+    root = tmp_path_factory.mktemp("dump")
+    return [(_bench(*_PLAIN, "--dump-outputs", str(root / n), gpus=1, full=False, timeout=240), root / n)
+            for n in ("a", "b")]
+
+
+def test_bench_plain_run_is_headline_only_and_dumps_outputs(plain_runs):
+    """Without ``--full`` only the headline phase runs (exactly --steps timed
+    steps), and ``--dump-outputs`` writes the dump step's loss and fp32 arenas."""
+    import numpy as np
+    out, d = plain_runs[0]
+    assert out["full"] is False and out["steps"] == 3 and out["warmup"] == 1 and out["n_gpus"] == 1
+    assert out["value"] > 0 and out["ms_per_step"] > 0 and out["dtype"] == "fp32" and out["unit"] == "images/s"
+    assert out["value"] == pytest.approx(32 * 1e3 / out["ms_per_step"], rel=1e-2)
+    assert set(out["phases"]) == {"headline"}
+    secondary = ("bf16_", "fp32_native_", "dense_", "ref_bs", "vgg16_", "lstm_", "bert_", "speedup_vs_dense")
+    assert not [k for k in out if k.startswith(secondary) or k.endswith("_error")]
+    assert out["replicas_consistent"] is None and out["collectives"] is None
+    # Gaussian-k with DGC momentum correction: the momentum state is the velocity arena
+    assert sorted(p.name for p in d.iterdir()) == ["loss.npy", "residuals.npy", "velocity.npy", "weights.npy"]
+    loss = np.load(d / "loss.npy")
+    # the dump step starts from the initial weights: the loss of an untrained 10-class net, ~ln 10
+    assert loss.dtype == np.float64 and loss.shape == (1,) and 1.5 < loss[0] < 4.0
+    for name in _DUMPED:
+        a = np.load(d / (name + ".npy"))
+        # resnet20: below the sampling cap, so the whole arena (>= every parameter)
+        assert a.dtype == np.float32 and a.ndim == 1 and a.size == out["dumped_outputs"][name] >= out["params"]
+        assert np.isfinite(a).all()
+    w, v, r = (np.load(d / (n + ".npy")) for n in _DUMPED)
+    # one real training step: non-trivial weights, and the unsent gradient mass is kept (velocity / residuals)
+    assert np.abs(w).max() > 0 and max(np.abs(v).max(), np.abs(r).max()) > 0
+
+
+def test_bench_dumped_outputs_repeat_from_run_to_run(plain_runs):
+    """Same arguments, same inputs, same outputs up to summation rounding.
+    Bound: the step's reductions are fp32 sums whose order the grad-weight
+    GEMMs' float atomics leave open; reordering n terms moves a sum by about
+    eps * sqrt(n) of its terms' magnitude (eps = 6e-8, n <= 32 * 32 * 32 here):
+    1e-5 of the array's largest magnitude, with 1e-4 allowed.  The compressor's
+    threshold can turn such a last-bit difference into a sent-or-kept entry; an
+    entry must lie within rounding of the threshold for that (expected 0.01 of
+    270 k), so at most 2 entries per array may differ by more."""
+    import numpy as np
+    (_, da), (_, db) = plain_runs
+    la, lb = np.load(da / "loss.npy"), np.load(db / "loss.npy")
+    print("loss", la[0], lb[0])
+    for name in _DUMPED:
+        a, b = np.load(da / (name + ".npy")), np.load(db / (name + ".npy"))
+        diff, tol = np.abs(a - b), 1e-4 * np.abs(a).max()
+        print(name, "max|a-b|", diff.max(), "max|a|", np.abs(a).max(), "beyond tol", int((diff > tol).sum()))
+    assert la[0] == pytest.approx(lb[0], rel=1e-4)
+    for name in _DUMPED:
+        a, b = np.load(da / (name + ".npy")), np.load(db / (name + ".npy"))
+        assert a.shape == b.shape
+        assert int((np.abs(a - b) > 1e-4 * np.abs(a).max()).sum()) <= 2, name
 
 
 def test_bench_phase_failure_keeps_headline(cuda):
