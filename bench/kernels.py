@@ -50,7 +50,7 @@ def main() -> int:
     ap.add_argument("--n", type=int, default=25_557_032)
     ap.add_argument("--json-out", default=None)
     ap.add_argument("--fit-out", default=None)
-    ap.add_argument("--only", default=None, help="comma list of sections: compress,round2,decompress,optim,bn,fit")
+    ap.add_argument("--only", default=None, help="comma list of sections: compress,round2,quality,decompress,optim,bn,fit")
     args = ap.parse_args()
     only = set(args.only.split(",")) if args.only else None
 
@@ -159,6 +159,23 @@ def main() -> int:
             sh = torch.empty(n, dtype=torch.bfloat16, device=dev)
             t = timeit(lambda: ops.apply_records_sgd_(wv, sh, recs, P, kc, 1.0 / P, 0.1))
             report("apply_records_sgd P=%d" % P, t, P * kc * 8 + kc * 10, "sparse SGD + bf16 shadow")
+
+    # ---------------- selection quality (record vs exact top-k, after a compress) ----------------
+    if want("quality"):
+        kc = 2 * k
+        bufs = ops.CompressBuffers(kc, dev)
+        g = g0.clone()
+        rq = torch.zeros(n, device=dev)
+        ops.compress_(g, rq, bufs, ops.MODE_GAUSSIAN, ec=True, zero_g=True, loops=3, z=gaussian_z(density), k=k,
+                      k_cap=kc, n_stats=args.n)
+        out = torch.zeros(8, dtype=torch.float64, device=dev)
+        ws = ops.quality_workspace(dev)
+        t = timeit(lambda: ops.selection_quality_(rq, bufs.record, k, kc, out, ws))
+        q = ops.quality_fields(out, kc)
+        # reads r three times (one histogram pass each) and the sent values four times
+        report("selection_quality", t, 3 * 4 * n + 4 * 4 * q["sent"],
+               "3 radix passes + final; sent %d, overlap %.3f, energy %.3f" % (q["sent"], q["topk_overlap"],
+                                                                                q["energy_captured"]))
 
     if args.fit_out or want("fit") and only is not None:
         from gaussiank_sgd_amd.utils import perf_model

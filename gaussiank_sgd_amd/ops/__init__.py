@@ -598,6 +598,103 @@ def sync_timeouts(bufs: CompressBuffers) -> int:
 
 
 # ---------------------------------------------------------------------------
+# selection quality
+# ---------------------------------------------------------------------------
+# layout of the float64[8] block written by selection_quality_ (gk_kernels.h kQual*)
+QUALITY_FIELDS = ("K", "c_gt", "overlap", "e_sel", "e_top", "e_all", "sent", "k_eff")
+
+
+def quality_workspace(device) -> Optional[torch.Tensor]:
+    """Per-bucket workspace of ``selection_quality_`` (None on the CPU)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        return None
+    require_native(torch.empty(0, device=device))
+    nb = int(_ops().quality_workspace_bytes())
+    return torch.zeros((nb + 7) // 8, dtype=torch.float64, device=device)
+
+
+def selection_quality_(r: torch.Tensor, record: torch.Tensor, k: int, k_cap: int, out: torch.Tensor,
+                       ws: Optional[torch.Tensor] = None) -> None:
+    """How good was the selection in ``record``?  Async on GPU.
+
+    ``r`` is the residual after ``compress_`` (the accumulator with the sent
+    entries zeroed) and ``record`` the packed record of that call, so
+    ``acc = r`` with ``acc[idx[j]] = val[j]`` for ``j < sent``.  With
+    ``k_eff = min(k, n)`` and ``key = abs_key``, ``out`` (float64[8],
+    ``QUALITY_FIELDS``; integer fields exact) receives
+
+        K        the k_eff-th largest key of acc
+        c_gt     #{i : key(acc[i]) > K}
+        overlap  #{j < sent : key(val[j]) > K} + min(#{j < sent : key(val[j]) == K}, k_eff - c_gt)
+        e_sel    sum_{j < sent} val[j]^2
+        e_top    sum_{key > K} acc^2 + (k_eff - c_gt) * f(K)^2   (f(K): the float with key K)
+        e_all    sum acc^2
+        sent, k_eff
+
+    Entries tied with the k-th magnitude count toward the overlap only up to
+    the free slots: overlap <= k_eff, with equality for an exact top-k record.
+    ``ws``: ``quality_workspace(device)`` (allocated per call when None); the
+    op resets it itself.
+    """
+    k, k_cap = int(k), int(k_cap)
+    if r.is_cuda:
+        require_native(r)
+        if ws is None:
+            ws = quality_workspace(r.device)
+        _ops().selection_quality(r, record, k, k_cap, out, ws)
+        return
+    with torch.no_grad():
+        n = r.numel()
+        if n < 1 or k < 1:
+            raise ValueError("need n >= 1 and k >= 1")
+        sent = min(max(int(record[0]), 0), k_cap)
+        idx = record[REC_HDR:REC_HDR + sent].long()
+        val = record[REC_HDR + k_cap:REC_HDR + k_cap + sent].view(torch.float32)
+        acc = r.detach().clone().view(-1)
+        acc[idx] = val
+        keys = abs_key(acc)
+        k_eff = min(k, n)
+        K = int(torch.topk(keys, k_eff).values[-1])
+        a64 = acc.double()
+        sq = a64 * a64
+        gt = keys > K
+        c_gt = int(gt.sum())
+        vkeys = abs_key(val)
+        slots = k_eff - c_gt
+        overlap = int((vkeys > K).sum()) + min(int((vkeys == K).sum()), slots)
+        fK = _key_thr(K)
+        res = [float(K), float(c_gt), float(overlap), float((val.double() ** 2).sum()),
+               float(sq[gt].sum()) + slots * fK * fK, float(sq.sum()), float(sent), float(k_eff)]
+        out.view(-1)[:len(res)].copy_(torch.tensor(res, dtype=torch.float64))
+
+
+def decode_quality(row: Sequence[float], k_cap: int) -> dict:
+    """One float64[8] block (host values) -> fields plus the derived ratios."""
+    d = dict(zip(QUALITY_FIELDS, row))
+    for f in ("K", "c_gt", "overlap", "sent", "k_eff"):
+        d[f] = int(d[f])
+    d["record_occupancy"] = d["sent"] / float(k_cap)
+    d["topk_overlap"] = d["overlap"] / float(d["k_eff"]) if d["k_eff"] else 0.0
+    d["energy_captured"] = d["e_sel"] / d["e_top"] if d["e_top"] else 0.0
+    d["energy_fraction"] = d["e_sel"] / d["e_all"] if d["e_all"] else 0.0
+    return d
+
+
+def quality_fields(out: torch.Tensor, k_cap: Optional[int] = None) -> dict:
+    """Decode a ``selection_quality_`` block (host sync; tests/diagnostics only).
+
+    Adds ``topk_overlap = overlap / k_eff``, ``energy_captured = e_sel / e_top``
+    (0 when e_top == 0), ``energy_fraction = e_sel / e_all`` and, when
+    ``k_cap`` is given, ``record_occupancy = sent / k_cap``."""
+    row = out.detach().view(-1)[:len(QUALITY_FIELDS)].cpu().tolist()
+    d = decode_quality(row, k_cap if k_cap else 1)
+    if not k_cap:
+        del d["record_occupancy"]
+    return d
+
+
+# ---------------------------------------------------------------------------
 # aggregation
 # ---------------------------------------------------------------------------
 def scatter_add_records_(dst: torch.Tensor, records: torch.Tensor, P: int, k_cap: int, scale: float,

@@ -47,6 +47,7 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
 HIP_SOURCES = [
     "kernels/compress.hip",
+    "kernels/quality.hip",
     "kernels/scatter.hip",
     "kernels/optim.hip",
     "kernels/bn_act.hip",

@@ -157,6 +157,24 @@ void arena_digest(at::Tensor x, at::Tensor out, at::Tensor ws) {
                    reinterpret_cast<uint64_t*>(ws.data_ptr<int64_t>()), cur_stream(x));
 }
 
+int64_t quality_workspace_bytes() { return (int64_t)gk::quality_workspace_bytes(); }
+
+void selection_quality(at::Tensor r, at::Tensor record, int64_t k, int64_t k_cap, at::Tensor out, at::Tensor ws) {
+  check_f32(r, "r");
+  check_dev(out, "out");
+  check_dev(ws, "ws");
+  TORCH_CHECK(record.scalar_type() == at::kInt && record.is_contiguous() && record.is_cuda() && k_cap >= 1 &&
+                  record.numel() >= gk::kRecHdr + 2 * k_cap,
+              "record: int32[4 + 2*k_cap]");
+  TORCH_CHECK(out.scalar_type() == at::kDouble && out.numel() >= gk::kQualFields, "out must be float64[8]");
+  TORCH_CHECK(r.numel() >= 1 && r.numel() < (int64_t)0x7fffffff && k >= 1, "need 1 <= n < 2^31 and k >= 1");
+  TORCH_CHECK(ws.nbytes() >= gk::quality_workspace_bytes(), "workspace too small");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(ws.data_ptr()) & 255) == 0, "ws must be 256-byte aligned");
+  c10::DeviceGuard guard(r.device());
+  gk::selection_quality(r.data_ptr<float>(), r.numel(), record.data_ptr<int32_t>(), k, k_cap, out.data_ptr<double>(),
+                        ws.data_ptr(), cur_stream(r));
+}
+
 void tensor_stats(at::Tensor x, at::Tensor ctrl, at::Tensor ws) {
   check_f32(x, "x");
   check_dev(ctrl, "ctrl");
@@ -1982,6 +2000,8 @@ TORCH_LIBRARY(gksgd, m) {
         "Tensor? lr_mult=None) -> ()");
   m.def("arena_digest(Tensor x, Tensor(a!) out, Tensor(b!) ws) -> ()");
   m.def("tensor_stats(Tensor x, Tensor(a!) ctrl, Tensor(b!) ws) -> ()");
+  m.def("quality_workspace_bytes() -> int", &quality_workspace_bytes);
+  m.def("selection_quality(Tensor r, Tensor record, int k, int k_cap, Tensor(a!) out, Tensor(b!) ws) -> ()");
   m.def("scatter_add_records(Tensor(a!) dst, Tensor records, int P, int k_cap, float scale, bool deterministic) -> ()");
   m.def("fill_zero(Tensor(a!) dst) -> ()");
   m.def("sign_bucket_workspace_bytes() -> int", &sign_bucket_workspace_bytes);
@@ -2152,6 +2172,7 @@ TORCH_LIBRARY(gksgd, m) {
 TORCH_LIBRARY_IMPL(gksgd, CUDA, m) {
   m.impl("compress", &compress);
   m.impl("tensor_stats", &tensor_stats);
+  m.impl("selection_quality", &selection_quality);
   m.impl("scatter_add_records", &scatter_add_records);
   m.impl("apply_records_sgd", &apply_records_sgd);
   m.impl("arena_digest", &arena_digest);

@@ -129,6 +129,25 @@ void compress(const CompressArgs& a, hipStream_t stream);
 void tensor_stats(const float* x, int64_t n, void* ctrl, void* ws, hipStream_t stream);
 
 // ---------------------------------------------------------------------------
+// Selection quality of a compressed bucket (quality.hip): the record against
+// the exact top-k of acc = r + scatter(record), k_eff = min(k, n).  out holds
+// kQualFields doubles (the integer fields are exact: all are < 2^53):
+//   [kQualK]       K, the k_eff-th largest abs_key of acc
+//   [kQualCgt]     #{i : key(acc[i]) > K}
+//   [kQualOverlap] #{j < sent : key(val[j]) > K} + min(#{j < sent : key(val[j]) == K}, k_eff - c_gt)
+//   [kQualEsel]    sum_{j < sent} val[j]^2
+//   [kQualEtop]    sum_{key > K} acc^2 + (k_eff - c_gt) * f(K)^2,  f(K) = the float with key K
+//   [kQualEall]    sum acc^2
+//   [kQualSent]    sent (record header, clamped to k_cap),  [kQualKeff] k_eff
+// ws: quality_workspace_bytes() bytes, 256-byte aligned; zeroed by the call.
+// ---------------------------------------------------------------------------
+constexpr int kQualK = 0, kQualCgt = 1, kQualOverlap = 2, kQualEsel = 3, kQualEtop = 4, kQualEall = 5,
+              kQualSent = 6, kQualKeff = 7, kQualFields = 8;
+size_t quality_workspace_bytes();
+void selection_quality(const float* r, int64_t n, const int32_t* record, int64_t k, int64_t k_cap, double* out,
+                       void* ws, hipStream_t stream);
+
+// ---------------------------------------------------------------------------
 // Sparse aggregation: dst[idx] += val * scale for every rank's record.
 // records: [P][4 + 2*k_cap] int32.  Atomic (default) or per-rank ordered.
 // ---------------------------------------------------------------------------

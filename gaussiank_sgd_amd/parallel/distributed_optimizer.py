@@ -172,6 +172,18 @@ class _DistributedOptimizer(torch.optim.Optimizer):
         # EVERY exchange (one blocking collective per exchange: a debug mode)
         self._check_order = _env_flag("GKSGD_CHECK_ORDER", False)
         self._next_launch = 0     # buckets launch strictly in index order
+        # selection_quality_every = N > 0: every N-th step each fused sparse
+        # bucket's record is scored against the exact top-k of its accumulator
+        # on device (ops.selection_quality_); rows wait in a device ring until
+        # collect_selection_quality().  0 (default): nothing is allocated or
+        # launched.  Skipped while a HIP graph captures (a captured step
+        # cannot advance the ring).
+        self._quality_every = max(0, int(opts.get("selection_quality_every",
+                                                  os.environ.get("GKSGD_SELECTION_QUALITY_EVERY", "0")) or 0))
+        self._q_dev: Optional[torch.Tensor] = None   # ring of float64[8] blocks, allocated on first use
+        self._q_meta: List[tuple] = []               # (iter, bucket, k_cap) of the ring's rows
+        self._q_host: List[dict] = []
+        self._q_capture_logged = False
 
         named_parameters = list(named_parameters) if named_parameters is not None else []
         if any(not isinstance(p, tuple) for p in named_parameters):
@@ -703,6 +715,8 @@ class _DistributedOptimizer(torch.optim.Optimizer):
                 ops.scatter_add_records_(g, gathered, max(self._world, 1), k_cap, 1.0 / max(self._world, 1), True)
             b.extra["agg_done"] = True
         self._log_selected(b.bufs.record[0:2])
+        if self._quality_every and self._fused_sparse and self.train_iter % self._quality_every == 0:
+            self._sample_quality(b, k_cap)
         if settings.LOGGING_GRADIENTS and self._rank == 0 and self._gradient_path and \
                 self.train_iter % max(1, settings.DUMP_GRAD_EVERY) == 0:
             self._queue_dump(b, b.slice(self._arena.residuals), rec, k_cap)
@@ -814,6 +828,68 @@ class _DistributedOptimizer(torch.optim.Optimizer):
             self._sel_n = 0
         self._sel_dev[self._sel_n].copy_(hdr.view(-1)[:2], non_blocking=True)
         self._sel_n += 1
+
+    _Q_RING = 4096   # selection-quality rows held on the device between drains
+
+    def _sample_quality(self, b, k_cap):
+        """Score bucket ``b``'s record against the exact top-k of its
+        accumulator (residual + record), on the stream it was compressed on;
+        the float64[8] block lands in the next ring row (no sync)."""
+        if self._is_cuda and torch.cuda.is_current_stream_capturing():
+            if not self._q_capture_logged:
+                self._q_capture_logged = True
+                logger.warning("selection_quality_every=%d: sampling is skipped while a HIP graph captures "
+                               "(captured steps are not sampled)", self._quality_every)
+            return
+        if self._q_dev is None:
+            self._q_dev = torch.zeros(self._Q_RING, len(ops.QUALITY_FIELDS), dtype=torch.float64, device=self._device)
+        if len(self._q_meta) == self._q_dev.shape[0]:
+            # ring full: flush to the host -- one sync per _Q_RING bucket-steps
+            self._q_host.extend(self._decode_quality(self._q_dev.cpu().tolist()))
+            self._q_meta = []
+        ws = b.extra.get("quality_ws")
+        if ws is None and self._is_cuda:
+            ws = b.extra["quality_ws"] = ops.quality_workspace(self._device)
+        k = self._compression.k_of(b.numel, self.get_current_density(b.name))
+        with trace.range("gk/b%d/quality" % b.index):
+            ops.selection_quality_(b.slice(self._arena.residuals), b.bufs.record, max(int(k), 1), k_cap,
+                                   self._q_dev[len(self._q_meta)], ws)
+        self._q_meta.append((self.train_iter, b.index, k_cap))
+
+    def _decode_quality(self, rows) -> List[dict]:
+        out = []
+        for (it, bi, k_cap), row in zip(self._q_meta, rows):
+            d = {"iter": it, "bucket": bi}
+            d.update(ops.decode_quality(row, k_cap))
+            out.append(d)
+        return out
+
+    def collect_selection_quality(self) -> List[dict]:
+        """Selection-quality rows sampled since the last call (one D2H copy):
+        one dict per sampled (iter, bucket) with the fields of
+        ``ops.selection_quality_`` and the derived ``record_occupancy``,
+        ``topk_overlap``, ``energy_captured`` and ``energy_fraction``.  Call
+        it between steps (after ``step()``), like the selected-count drain."""
+        n = len(self._q_meta)
+        rows = self._decode_quality(self._q_dev[:n].cpu().tolist()) if n else []
+        out = self._q_host + rows
+        self._q_host = []
+        self._q_meta = []
+        return out
+
+    def selection_quality_summary(self, rows: Optional[List[dict]] = None) -> dict:
+        """Means of the four metrics over ``rows`` (default: the rows since the
+        last collect) and ``compression_ratio_used``: dense fp32 gradient bytes
+        over the 8 bytes (index + value) of every entry actually sent per
+        step.  Empty when nothing was sampled."""
+        rows = self.collect_selection_quality() if rows is None else rows
+        if not rows:
+            return {}
+        out = {m: float(np.mean([r[m] for r in rows]))
+               for m in ("record_occupancy", "topk_overlap", "energy_captured", "energy_fraction")}
+        sent_per_step = float(np.mean([r["sent"] for r in rows])) * len(self._arena.buckets)
+        out["compression_ratio_used"] = int(np.sum(self._sizes)) * 4.0 / (8.0 * sent_per_step) if sent_per_step else 0.0
+        return out
 
     def _queue_dump(self, b, r, rec, k_cap):
         """Sampled gradient dump: acc = r_new + scatter(own record), async D2H."""
@@ -1223,7 +1299,11 @@ def DistributedOptimizer(optimizer, named_parameters=None, compression=None, is_
     Extra keyword options (MI355X build): ``compress_single_rank``,
     ``deterministic``, ``fused_optimizer``, ``zero_grad_in_step``, ``overlap``,
     ``density_warmup`` (True | False | list), ``native_rccl``, ``profiling``,
-    ``planner_preset`` ('mi355x' | 'reference').
+    ``planner_preset`` ('mi355x' | 'reference'), ``selection_quality_every``
+    (N > 0: every N-th step each fused sparse bucket's record is scored
+    against the exact top-k of its accumulator on device, rows from
+    ``collect_selection_quality()``; default ``GKSGD_SELECTION_QUALITY_EVERY``
+    or 0 = off; steps captured into a HIP graph are not sampled).
     """
     from ..compression import compressors
     if compression is None or isinstance(compression, str):

@@ -38,7 +38,7 @@ def ssgd(dnn, dataset, data_dir, nworkers, lr, batch_size, nsteps_update, max_ep
          density_warmup=True, deterministic=False, max_iters=None, compress_single_rank=False, saved_dir=".",
          bf16_shadow=True, momentum_correction=False, k_cap_factor=None, overlap=True, dump_grad_every=None,
          metrics_dir=None, f32_matmul=None, train_samples=None, checkpoint_every=2, save_final=False,
-         hip_graph=False):
+         hip_graph=False, selection_quality_every=None):
     rank = hvd.rank()
     device = "cpu"
     if torch.cuda.is_available():
@@ -98,13 +98,15 @@ def ssgd(dnn, dataset, data_dir, nworkers, lr, batch_size, nsteps_update, max_ep
     elif dnn == "lstman4":
         norm_clip = 400
 
+    # --selection-quality-every N: None leaves the optimizer's default (GKSGD_SELECTION_QUALITY_EVERY, else off)
+    quality_opt = {} if selection_quality_every is None else {"selection_quality_every": int(selection_quality_every)}
     optimizer = hvd.DistributedOptimizer(trainer.optimizer, named_parameters=trainer.net.named_parameters(),
                                          compression=compressors[compressor], is_sparse=is_sparse, density=density,
                                          seq_layernames=seq_layernames, layerwise_times=layerwise_times,
                                          norm_clip=None, threshold=threshold, writer=None,
                                          gradient_path=gradient_path, density_warmup=density_warmup,
                                          deterministic=deterministic, compress_single_rank=compress_single_rank,
-                                         momentum_correction=momentum_correction, overlap=overlap)
+                                         momentum_correction=momentum_correction, overlap=overlap, **quality_opt)
     comp_state = getattr(trainer, "_pending_compression", None)
     if own_ck is not None:
         from ..utils.checkpoint import load_checkpoint
@@ -184,13 +186,17 @@ def ssgd(dnn, dataset, data_dir, nworkers, lr, batch_size, nsteps_update, max_ep
                 sel = optimizer._collect_selected() if hasattr(optimizer, "_collect_selected") else []
                 per_iter_sel = float(np.mean(sel)) * len(optimizer.arena.buckets) if sel else 0.0
                 ratio = optimizer.wire_compression_ratio() if hasattr(optimizer, "wire_compression_ratio") else 1.0
+                # with selection-quality sampling on: the window's mean record_occupancy, topk_overlap,
+                # energy_captured, energy_fraction and compression_ratio_used (absent when off)
+                quality = optimizer.selection_quality_summary() if getattr(optimizer, "_quality_every", 0) else {}
                 metrics.write(iter=int(trainer.get_train_iter()), epoch=epoch, rank=rank, time_per_iter=time_per_iter,
                               samples_per_s=speed, samples_per_s_node=speed * nworkers,
                               density=optimizer.get_current_density(),
                               selected_per_iter=per_iter_sel,
                               compression_ratio=ratio,
                               loss=float(trainer.current_loss()),
-                              hbm_gb=(torch.cuda.max_memory_allocated() / 2 ** 30) if trainer.is_cuda else 0.0)
+                              hbm_gb=(torch.cuda.max_memory_allocated() / 2 ** 30) if trainer.is_cuda else 0.0,
+                              **quality)
                 times = []
             done += 1
             if max_iters is not None and done >= max_iters:
@@ -266,6 +272,11 @@ def build_parser():
     p.add_argument("--hip-graph", action="store_true",
                    help="replay the whole training step as one HIP graph (one GPU process, non-recurrent models; "
                         "what bench.py does for its reference-batch phases)")
+    p.add_argument("--selection-quality-every", type=int, default=None, metavar="N",
+                   help="every N steps score each bucket's record against the exact top-k of its accumulator on "
+                        "device (record_occupancy, topk_overlap, energy_captured, energy_fraction and "
+                        "compression_ratio_used in the metrics lines); 0 = off (default: "
+                        "GKSGD_SELECTION_QUALITY_EVERY, else off)")
     p.add_argument("--save-final", action="store_true",
                    help="every rank saves its checkpoint at the end of the run (resume with --pretrain)")
     return p
@@ -304,7 +315,8 @@ def main(argv=None):
                 bf16_shadow=not args.no_bf16_shadow, momentum_correction=args.momentum_correction,
                 k_cap_factor=args.k_cap_factor, overlap=not args.no_overlap, dump_grad_every=args.dump_grad_every,
                 metrics_dir=relative_path, f32_matmul=args.f32_matmul, train_samples=args.train_samples,
-                checkpoint_every=args.checkpoint_every, save_final=args.save_final, hip_graph=args.hip_graph)
+                checkpoint_every=args.checkpoint_every, save_final=args.save_final, hip_graph=args.hip_graph,
+                selection_quality_every=args.selection_quality_every)
 
 
 if __name__ == "__main__":
