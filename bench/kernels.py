@@ -236,6 +236,27 @@ def main() -> int:
     report("fused_sgd (w,m,g)", t, 5 * 4 * n)
     t = timeit(lambda: ops.fused_sgd_(w, m, gr, chunks, hp, zero_grad=True, w_bf16=sh))
     report("fused_sgd + zero g + bf16 shadow", t, 6 * 4 * n + 2 * n)
+    # Adam / AdamW on arenas of its own (the rows below keep w, m, gr): same chunk table, two more streams
+    wa, ga = torch.randn(n, device=dev), torch.randn(n, device=dev)
+    ma, va = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
+    stp = torch.zeros((), dtype=torch.float32, device=dev)
+    hpa = [dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, decoupled=True)]
+    t = timeit(lambda: ops.fused_adam_(wa, ma, va, ga, chunks, hpa, stp, zero_grad=False))
+    report("fused_adam (w,m,v,g)", t, 7 * 4 * n, "incl. the one-thread step tick")
+    t = timeit(lambda: ops.fused_adam_(wa, ma, va, ga, chunks, hpa, stp, zero_grad=True, w_bf16=sh))
+    report("fused_adam + zero g + bf16 shadow", t, 8 * 4 * n + 2 * n)
+    # context: torch's multi-tensor AdamW over the same arena cut into 161 tensors (ResNet-50's count);
+    # it neither zeroes g nor writes the shadow
+    ga.normal_()
+    piece = n // 161 // 64 * 64
+    cuts = [(i * piece, (i + 1) * piece if i < 160 else n) for i in range(161)]
+    ps = [wa[a:b].detach().requires_grad_(True) for a, b in cuts]
+    for p, (a, b) in zip(ps, cuts):
+        p.grad = ga[a:b]
+    topt = torch.optim.AdamW(ps, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, foreach=True)
+    t = timeit(topt.step)
+    report("torch AdamW foreach (context)", t, 7 * 4 * n, "161 tensors, host-side step count")
+    del topt, ps, wa, ga, ma, va
     u = torch.zeros(n, device=dev)
     t = timeit(lambda: ops.momentum_correct_(u, gr, w, chunks, 0, chunks.numel() // 2, hp))
     report("momentum_correct (u,g,w)", t, 5 * 4 * n)

@@ -14,6 +14,7 @@ Packed record layout (one per rank and bucket, int32 words)::
 """
 from __future__ import annotations
 
+import math
 import os
 import threading
 from pathlib import Path
@@ -943,6 +944,58 @@ def fused_sgd_(w: torch.Tensor, m: Optional[torch.Tensor], g: torch.Tensor, chun
                 ms.mul_(mom).add_(d, alpha=1 - float(p.get("dampening", 0.0)))
             d = d + mom * ms if p.get("nesterov", False) else ms
         ws.add_(d, alpha=-float(p["lr"]) * lm)
+        if w_bf16 is not None:
+            w_bf16[start:start + ln].copy_(ws)
+        if zero_grad:
+            g[start:start + ln].zero_()
+
+
+def fused_adam_(w: torch.Tensor, m: torch.Tensor, v: torch.Tensor, g: torch.Tensor, chunks: torch.Tensor,
+                groups: Sequence[dict], step: torch.Tensor, zero_grad: bool = True,
+                grad_scale: Optional[torch.Tensor] = None, w_bf16: Optional[torch.Tensor] = None,
+                lr_mult: Optional[torch.Tensor] = None) -> None:
+    """torch.optim.Adam / AdamW (single-tensor, no amsgrad / maximize) over the chunk table.
+
+    groups: dicts with lr, betas, eps, weight_decay, decoupled (True: AdamW's
+    ``w *= 1 - lr * wd``; False: Adam's ``g += wd * w``).  ``step``: one fp32
+    scalar on w's device holding the number of steps taken; it is incremented
+    here (on the GPU by a one-thread launch ahead of the update, which reads
+    the new count for the bias corrections), never read by the host -- eager
+    calls and HIP-graph replays take the same path.  ``grad_scale``, ``w_bf16``
+    and ``lr_mult`` as in ``fused_sgd_``; ``lr_mult`` also scales the decoupled
+    decay term.  ``eps`` must be positive: a slot with m = v = 0 (the arena's
+    padding, an element that never saw a gradient) is 0 / (0 + eps) = 0 and
+    stays exactly 0; with eps = 0 it would be 0 / 0.
+    """
+    if any(not float(p["eps"]) > 0.0 for p in groups):
+        raise ValueError("fused_adam_ needs eps > 0 in every group (eps = 0 turns zero slots into 0 / 0)")
+    if w.is_cuda:
+        require_native(w)
+        _ops().fused_adam(w, m, v, g, chunks, step, [float(p["lr"]) for p in groups],
+                          [float(p["betas"][0]) for p in groups], [float(p["betas"][1]) for p in groups],
+                          [float(p["eps"]) for p in groups], [float(p.get("weight_decay", 0.0)) for p in groups],
+                          [int(bool(p.get("decoupled", False))) for p in groups], bool(zero_grad), grad_scale,
+                          w_bf16, lr_mult)
+        return
+    step += 1
+    t = float(step)
+    gs = float(grad_scale) if grad_scale is not None else 1.0
+    lm = float(lr_mult) if lr_mult is not None else 1.0
+    for start, ln, gi, _ in _decode_chunks(chunks):
+        p = groups[gi]
+        lr = float(p["lr"]) * lm
+        b1, b2 = float(p["betas"][0]), float(p["betas"][1])
+        wd = float(p.get("weight_decay", 0.0))
+        ws, ms, vs = w[start:start + ln], m[start:start + ln], v[start:start + ln]
+        d = g[start:start + ln] * gs
+        if p.get("decoupled", False):
+            ws.mul_(1.0 - lr * wd)
+        elif wd != 0:
+            d = d + wd * ws
+        ms.lerp_(d, 1.0 - b1)
+        vs.mul_(b2).addcmul_(d, d, value=1.0 - b2)
+        denom = (vs.sqrt() / math.sqrt(1.0 - b2 ** t)).add_(float(p["eps"]))
+        ws.addcdiv_(ms, denom, value=-lr / (1.0 - b1 ** t))
         if w_bf16 is not None:
             w_bf16[start:start + ln].copy_(ws)
         if zero_grad:

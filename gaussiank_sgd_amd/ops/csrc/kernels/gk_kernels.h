@@ -207,6 +207,33 @@ struct SgdArgs {
 };
 void fused_sgd(const SgdArgs& a, hipStream_t stream);
 
+// torch.optim.Adam / AdamW (single-tensor, no amsgrad / maximize) over the
+// same chunk table.  The hyper-parameters stay double: torch derives the bias
+// corrections, lr / bc1 and 1 - lr * wd from Python floats before it rounds.
+struct AdamGroup {
+  double lr, beta1, beta2, eps, weight_decay;
+  int decoupled;      // AdamW: w *= 1 - lr * wd; otherwise g += wd * w
+  int pad0;
+};
+struct AdamArgs {
+  float* w = nullptr;
+  float* m = nullptr;        // exp_avg
+  float* v = nullptr;        // exp_avg_sq
+  float* g = nullptr;
+  const Chunk* chunks = nullptr;
+  int nchunks = 0;
+  AdamGroup groups[kMaxGroups];
+  int ngroups = 0;
+  int zero_grad = 1;
+  float* step = nullptr;              // device step count (fp32 scalar, torch's capturable convention)
+  const float* grad_scale = nullptr;  // optional device scalar (clip coefficient)
+  uint16_t* w_bf16 = nullptr;         // optional bf16 shadow of w written in the same pass
+  const float* lr_mult = nullptr;     // optional device scalar multiplying every group's lr (graph replay)
+};
+// Two launches on `stream`: *step += 1 (one thread), then the update, whose
+// workgroups read the new count for the bias corrections.  No host read.
+void fused_adam(const AdamArgs& a, hipStream_t stream);
+
 // DGC momentum correction over a chunk range: u = mu*u + g + wd*w; g = u.
 struct McArgs {
   float* u = nullptr;

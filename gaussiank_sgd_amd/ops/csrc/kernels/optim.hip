@@ -7,6 +7,11 @@
 //                    Reference: dl_trainer.py:212-228 (two param groups),
 //                    dl_trainer.py:839-873 (_step), torch SGD via
 //                    distributed_optimizer.py:546.
+//   fused_adam       torch.optim.Adam / AdamW (single-tensor, no amsgrad) with the
+//                    same chunk table, gradient zeroing, bf16 shadow and device
+//                    scalars; the step count is a device scalar bumped by a
+//                    one-thread launch ahead of the update, so eager steps and
+//                    HIP-graph replays take one path with no host read.
 //   segmented_sumsq  per-tensor ||w||^2, ||g||^2 (LARS trust ratios)
 //   fused_lars       K13: lars.py:67-134 (trust ratio clamp [0,50], grad clamp
 //                    +-10, acceleration buffer initialised to ones)
@@ -77,6 +82,98 @@ __global__ __launch_bounds__(kBlock) void fused_sgd_kernel(SgdArgs a) {
     if (use_m) m[i] = mv;
     if (a.zero_grad) g[i] = 0.f;
     if (a.w_bf16) a.w_bf16[c.start + i] = f2bf(w[i]);
+  }
+}
+
+// ---- Adam / AdamW -------------------------------------------------------------
+// Per-workgroup constants of one chunk's param group at the current step.
+struct AdamCoef {
+  float omb1, beta2, omb2;   // 1 - beta1, beta2, 1 - beta2
+  float decay;               // AdamW: 1 - lr * wd (1 when coupled)
+  float wd;                  // Adam: wd added to the gradient (0 when decoupled)
+  float step_size;           // lr / (1 - beta1^t)
+  float bc2_sqrt;            // sqrt(1 - beta2^t)
+  float eps;
+};
+
+__global__ void adam_tick_kernel(float* __restrict__ step) { *step += 1.f; }
+
+// torch's single-tensor order of operations; sqrtf and '/' are the correctly
+// rounded ones (with eps = 1e-8 and the tiny v of a sparsified gradient the
+// approximate rcp / rsq are visible).  A slot with w = g = m = v = 0 (padding)
+// stays exactly 0 because eps > 0 (checked by the binding): 0 / (0 + eps).
+__device__ __forceinline__ float adam_elem(float w, float& m, float& v, float g, const AdamCoef& k, float gs) {
+  float d = g * gs;
+  if (k.wd != 0.f) d = fmaf(k.wd, w, d);
+  w *= k.decay;
+  m = fmaf(k.omb1, d - m, m);
+  v = fmaf(k.omb2 * d, d, k.beta2 * v);
+  const float denom = sqrtf(v) / k.bc2_sqrt + k.eps;
+  return fmaf(-k.step_size, m / denom, w);
+}
+
+__global__ __launch_bounds__(kBlock) void fused_adam_kernel(AdamArgs a) {
+  const Chunk c = a.chunks[blockIdx.x];
+  // bias corrections from the device step count, in double, once per workgroup
+  // (a per-element pow would make this streaming pass compute-bound)
+  __shared__ AdamCoef sk;
+  if (threadIdx.x == 0) {
+    const AdamGroup p = a.groups[c.group];
+    const double t = (double)*a.step;
+    double lr = p.lr;
+    if (a.lr_mult) lr *= (double)*a.lr_mult;   // lr schedule of a captured graph; scales the decoupled decay too
+    const double bc1 = 1.0 - pow(p.beta1, t);
+    const double bc2 = 1.0 - pow(p.beta2, t);
+    AdamCoef k;
+    k.omb1 = (float)(1.0 - p.beta1);
+    k.beta2 = (float)p.beta2;
+    k.omb2 = (float)(1.0 - p.beta2);
+    k.decay = p.decoupled ? (float)(1.0 - lr * p.weight_decay) : 1.f;
+    k.wd = p.decoupled ? 0.f : (float)p.weight_decay;
+    k.step_size = (float)(lr / bc1);
+    k.bc2_sqrt = (float)sqrt(bc2);
+    k.eps = (float)p.eps;
+    sk = k;
+  }
+  __syncthreads();
+  const AdamCoef k = sk;
+  const float gs = a.grad_scale ? *a.grad_scale : 1.f;
+  float* w = a.w + c.start;
+  float* m = a.m + c.start;
+  float* v = a.v + c.start;
+  float* g = a.g + c.start;
+  const int n4 = c.len >> 2;
+  float4* w4 = reinterpret_cast<float4*>(w);
+  float4* m4 = reinterpret_cast<float4*>(m);
+  float4* v4 = reinterpret_cast<float4*>(v);
+  float4* g4 = reinterpret_cast<float4*>(g);
+  for (int i = threadIdx.x; i < n4; i += kBlock) {
+    float4 wv = w4[i];
+    float4 mv = m4[i];
+    float4 vv = v4[i];
+    const float4 gv = g4[i];
+    wv.x = adam_elem(wv.x, mv.x, vv.x, gv.x, k, gs);
+    wv.y = adam_elem(wv.y, mv.y, vv.y, gv.y, k, gs);
+    wv.z = adam_elem(wv.z, mv.z, vv.z, gv.z, k, gs);
+    wv.w = adam_elem(wv.w, mv.w, vv.w, gv.w, k, gs);
+    w4[i] = wv;
+    m4[i] = mv;
+    v4[i] = vv;
+    if (a.zero_grad) g4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (a.w_bf16) {
+      const uint32_t lo = (uint32_t)f2bf(wv.x) | ((uint32_t)f2bf(wv.y) << 16);
+      const uint32_t hi = (uint32_t)f2bf(wv.z) | ((uint32_t)f2bf(wv.w) << 16);
+      reinterpret_cast<uint2*>(a.w_bf16 + c.start)[i] = make_uint2(lo, hi);
+    }
+  }
+  for (int i = (n4 << 2) + threadIdx.x; i < c.len; i += kBlock) {
+    float mv = m[i], vv = v[i];
+    const float wn = adam_elem(w[i], mv, vv, g[i], k, gs);
+    w[i] = wn;
+    m[i] = mv;
+    v[i] = vv;
+    if (a.zero_grad) g[i] = 0.f;
+    if (a.w_bf16) a.w_bf16[c.start + i] = f2bf(wn);
   }
 }
 
@@ -266,6 +363,12 @@ __global__ __launch_bounds__(kBlock) void scale_kernel(float* __restrict__ x, in
 void fused_sgd(const SgdArgs& a, hipStream_t s) {
   if (a.nchunks <= 0) return;
   hipLaunchKernelGGL(fused_sgd_kernel, dim3(a.nchunks), dim3(kBlock), 0, s, a);
+}
+
+void fused_adam(const AdamArgs& a, hipStream_t s) {
+  if (a.nchunks <= 0) return;
+  hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, s, a.step);
+  hipLaunchKernelGGL(fused_adam_kernel, dim3(a.nchunks), dim3(kBlock), 0, s, a);
 }
 
 void momentum_correct(const McArgs& a, hipStream_t s) {

@@ -7,7 +7,7 @@ hook COPIES the gradient into it and, after the exchange, ``p.grad`` is
 re-pointed into the buffer.
 
 MI355X design: one flat fp32 arena per role (weights, gradients, residuals,
-momentum), laid out bucket by bucket in backward order.  ``p.data`` and
+momentum, Adam's second moment), laid out bucket by bucket in backward order.  ``p.data`` and
 ``p.grad`` are views into the arenas from the start, so autograd accumulates
 straight into the bucket (no pack copy, K10 eliminated), a bucket is a
 contiguous slice the HIP kernels stream with 16-byte loads, and the fused
@@ -115,7 +115,8 @@ class GradArena:
         self.weights = torch.zeros(self.total, dtype=torch.float32, device=dev)
         self.grads = torch.zeros(self.total, dtype=torch.float32, device=dev)
         self.residuals = torch.zeros(self.total, dtype=torch.float32, device=dev) if with_residuals else None
-        self.momentum: Optional[torch.Tensor] = None
+        self.momentum: Optional[torch.Tensor] = None        # SGD momentum / LARS acceleration / Adam exp_avg
+        self.second_moment: Optional[torch.Tensor] = None   # Adam exp_avg_sq
         self.grad_views: Dict[str, torch.Tensor] = {}
         self.weight_views: Dict[str, torch.Tensor] = {}
         with torch.no_grad():
@@ -144,6 +145,11 @@ class GradArena:
         if self.momentum is None:
             self.momentum = torch.full((self.total,), fill, dtype=torch.float32, device=self.device)
         return self.momentum
+
+    def ensure_second_moment(self) -> torch.Tensor:
+        if self.second_moment is None:
+            self.second_moment = torch.zeros(self.total, dtype=torch.float32, device=self.device)
+        return self.second_moment
 
     def check_grad(self, key: str, p: torch.nn.Parameter) -> None:
         """Re-attach p.grad to the arena if someone replaced it (e.g. zero_grad(set_to_none))."""

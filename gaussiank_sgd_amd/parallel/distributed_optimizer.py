@@ -27,11 +27,15 @@ MI355X execution model (what is different, and why):
     the host never blocks.
   * ``step()`` runs ONE fused SGD (or LARS) launch over the whole arena (wd,
     momentum, nesterov, per-group hyper-parameters) and zeroes the gradient
-    arena in the same pass.
+    arena in the same pass.  ``torch.optim.Adam`` / ``AdamW`` get the same
+    one-launch update (``ops.fused_adam_``); their step count is ONE fp32
+    device scalar that every ``state[p]["step"]`` aliases, incremented on the
+    device, so a captured HIP graph follows it.
 """
 from __future__ import annotations
 
 import contextlib
+import inspect
 import math
 import os
 import time
@@ -90,6 +94,11 @@ class _DistributedOptimizer(torch.optim.Optimizer):
                  gradient_path=None, _gk_opts=None):
         opts = dict(_gk_opts or {})
         defaults = opts.pop("defaults", {}) or {}
+        # torch.optim.AdamW sets decoupled_weight_decay itself and does not take it back as an
+        # argument; any other default its class refuses still raises
+        if "decoupled_weight_decay" in defaults and "decoupled_weight_decay" not in \
+                inspect.signature(self.__class__.__mro__[1].__init__).parameters:
+            defaults = {k: v for k, v in defaults.items() if k != "decoupled_weight_decay"}
         super(self.__class__, self).__init__(params, **defaults)
         self._compression = compression
         self._sparse = is_sparse
@@ -1020,6 +1029,7 @@ class _DistributedOptimizer(torch.optim.Optimizer):
 
     def _setup_fused_update(self):
         self._fused_kind = None
+        self._adam_capable = False    # "adam" was chosen here (it may be dropped and restored with the state)
         base = self._base_cls
         if not self._fused_optim or base is None:
             return
@@ -1034,6 +1044,15 @@ class _DistributedOptimizer(torch.optim.Optimizer):
             self._fused_kind = "sgd"
         elif base is LARS:
             self._fused_kind = "lars"
+        elif base in (torch.optim.Adam, torch.optim.AdamW):
+            # eps <= 0: the all-zero padding slots would become 0 / 0 (torch has no padding)
+            if any(g.get("amsgrad", False) or g.get("maximize", False) or g.get("differentiable", False)
+                   or not float(g["eps"]) > 0.0 for g in self.param_groups):
+                return
+            self._fused_kind = "adam"
+            self._adam_capable = True
+            # the step count of every parameter: one device scalar (torch's capturable convention)
+            self._adam_step = torch.zeros((), dtype=torch.float32, device=self._device)
         else:
             return
         group_of_key = {}
@@ -1102,7 +1121,42 @@ class _DistributedOptimizer(torch.optim.Optimizer):
                 if buf is not None and buf.data_ptr() != view.data_ptr():
                     view.copy_(buf)
                 st["acceleration"] = view
+        elif self._fused_kind == "adam":
+            params = [p for g in self.param_groups for p in g["params"] if p in self._parameter_names]
+            shared = self._adam_step
+            # step counts handed in (factory / load_state_dict); a parameter without state has taken none
+            steps = set()
+            for p in params:
+                s = self.state[p].get("step")
+                if s is None:
+                    steps.add(0.0)
+                elif not (torch.is_tensor(s) and s.data_ptr() == shared.data_ptr()):
+                    steps.add(float(s))
+            if len(steps) > 1:
+                # one bias correction per launch: parameters at different steps keep torch's own update
+                logger.warning("Adam state with different per-parameter step counts %s: unfused torch update",
+                               sorted(steps))
+                self._fused_kind = None
+                self._state_dirty = False
+                return
+            if steps:
+                shared.fill_(steps.pop())
+            m = arena.ensure_momentum(0.0)
+            v = arena.ensure_second_moment()
+            for p in params:
+                key = self._parameter_names[p]
+                st = self.state[p]
+                for name, ar in (("exp_avg", m), ("exp_avg_sq", v)):
+                    view = arena.view_of(ar, key)
+                    buf = st.get(name)
+                    if buf is not None and buf.data_ptr() != view.data_ptr():
+                        view.copy_(buf)
+                    st[name] = view
+                st["step"] = shared
         self._state_dirty = False
+
+    def _adam_decoupled(self, g) -> bool:
+        return self._base_cls is torch.optim.AdamW or bool(g.get("decoupled_weight_decay", False))
 
     def _fused_step(self):
         arena = self._arena
@@ -1145,6 +1199,15 @@ class _DistributedOptimizer(torch.optim.Optimizer):
             if any(self._group_first):
                 self._group_first = [False] * len(self._group_first)
                 self._adopt_state()
+        elif self._fused_kind == "adam":
+            # one tick of the device step count + one update launch; the bias
+            # corrections are derived on the device, so this is also what a
+            # captured graph replays
+            groups = [{"lr": g["lr"], "betas": g["betas"], "eps": g["eps"], "weight_decay": g.get("weight_decay", 0.0),
+                       "decoupled": self._adam_decoupled(g)} for g in self.param_groups]
+            ops.fused_adam_(arena.weights, arena.momentum, arena.second_moment, arena.grads, self._chunks, groups,
+                            self._adam_step, zero_grad=self._zero_grad_in_step,
+                            w_bf16=getattr(arena, "shadow", None), lr_mult=self._lr_mult)
         else:
             self._seg_sumsq.zero_()
             ops.segmented_sumsq_(arena.weights, arena.grads, self._chunks, self._seg_sumsq)
@@ -1172,6 +1235,9 @@ class _DistributedOptimizer(torch.optim.Optimizer):
             self._exchanger.check()   # native engine: raise if its watchdog aborted a hung collective
         if not self.local:
             self.synchronize()
+        if self._fused_kind == "adam" and (self._state_dirty or self._arena.second_moment is None):
+            with torch.no_grad():
+                self._adopt_state()    # may fall back to the unfused update (differing step counts)
         if self._fused_kind is not None:
             loss = None
             if closure is not None:
@@ -1196,9 +1262,20 @@ class _DistributedOptimizer(torch.optim.Optimizer):
             ops.fill_zero_(self._arena.grads)
         self._grads_zero = True
 
+    def state_dict(self):
+        sd = super(self.__class__, self).state_dict()
+        if self._fused_kind == "adam":
+            # every state[p]["step"] is the one device scalar: hand out one counter
+            # per parameter, as a plain torch.optim.Adam(W) that loads this expects
+            sd["state"] = {k: ({**st, "step": st["step"].clone()} if torch.is_tensor(st.get("step")) else st)
+                           for k, st in sd["state"].items()}
+        return sd
+
     def load_state_dict(self, state_dict):
         super(self.__class__, self).load_state_dict(state_dict)
         self._state_dirty = True
+        if self._adam_capable:
+            self._fused_kind = "adam"    # the new state decides again (differing step counts drop it)
         if self._fused_kind is not None:
             with torch.no_grad():
                 self._adopt_state()
@@ -1240,10 +1317,10 @@ class _DistributedOptimizer(torch.optim.Optimizer):
     def broadcast_state(self, root_rank: int = 0) -> None:
         """Make the REPLICATED optimizer state identical on every rank after a
         resume: the density-schedule / iteration position (``train_epoch``,
-        ``train_iter``) and the global momentum (or LARS acceleration) buffers
-        are taken from ``root_rank``.  Per-rank state -- error-feedback
-        residuals and DGC local velocities -- is NOT touched: every rank loads
-        its own (``load_compression_state``).
+        ``train_iter``) and the global momentum (or LARS acceleration, or Adam
+        moment) buffers and Adam's step count are taken from ``root_rank``.
+        Per-rank state -- error-feedback residuals and DGC local velocities --
+        is NOT touched: every rank loads its own (``load_compression_state``).
 
         The reference restores only rank 0's weights and epoch / iteration
         (dist_trainer.py:26-33,57; dl_trainer.py:285-290), so its resume is
@@ -1257,6 +1334,11 @@ class _DistributedOptimizer(torch.optim.Optimizer):
         self.train_epoch, self.train_iter = int(pos[0]), int(pos[1])
         self._plan_check_due = True
         if self._world <= 1 and comm.backend() != "loopback":
+            return
+        if self._adam_capable:
+            # before the local kind is looked at: a rank that dropped to the unfused
+            # update on its own state must still enter the root's collectives
+            self._broadcast_adam_state(root_rank)
             return
         kind = self._fused_kind
         if kind is None:
@@ -1283,6 +1365,37 @@ class _DistributedOptimizer(torch.optim.Optimizer):
                     if p in self._parameter_names:
                         self.state[p][key] = self._arena.view_of(m, self._parameter_names[p])
                 self._group_first[gi] = False
+        self._state_dirty = False
+
+    def _broadcast_adam_state(self, root_rank: int) -> None:
+        """Both moment arenas and the device step count from the root (two
+        arena collectives and one scalar); every rank's state entries are views
+        of those arenas (``_adopt_state``), so they follow."""
+        params = [p for g in self.param_groups for p in g["params"] if p in self._parameter_names]
+        have = all("exp_avg" in self.state.get(p, {}) for p in params)
+        have = broadcast_object(have, root_rank)
+        if not have:
+            return
+        with torch.no_grad():
+            if self._rank != root_rank:
+                for p in params:           # the root's state replaces whatever this rank held,
+                    self.state.pop(p, None)
+                self._fused_kind = "adam"  # and with it this rank's own reason to run unfused
+                self._state_dirty = True
+            if self._fused_kind == "adam" and (self._state_dirty or self._arena.second_moment is None):
+                self._adopt_state()    # root: buffers -> arena views; others: zero arenas
+            # the root's kind decides for every rank: one sequence of collectives
+            if not broadcast_object(self._fused_kind == "adam", root_rank):
+                # the root's parameters are at different steps: every rank keeps torch's update
+                if self._fused_kind == "adam":
+                    self._fused_kind = None
+                    for p in params:
+                        self.state[p]["step"] = self.state[p]["step"].clone()
+                broadcast_optimizer_state(self, root_rank)
+                return
+            broadcast_(self._arena.momentum, root_rank)
+            broadcast_(self._arena.second_moment, root_rank)
+            broadcast_(self._adam_step.view(1), root_rank)
         self._state_dirty = False
 
     @property

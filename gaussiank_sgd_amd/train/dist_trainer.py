@@ -14,7 +14,9 @@ Launch one process per GPU: ``torchrun --nproc-per-node N -m
 gaussiank_sgd_amd.train.dist_trainer ...`` (or mpirun: OMPI_* variables are
 understood).  New flags: ``--synthetic`` (always on: no datasets offline),
 ``--amp bf16``, ``--channels-last``, ``--density-warmup/--no-density-warmup``,
-``--deterministic``, ``--max-iters``, ``--compress-single-rank``.
+``--deterministic``, ``--max-iters``, ``--compress-single-rank``,
+``--optimizer {sgd,adam,adamw}`` with ``--adam-beta1 --adam-beta2 --adam-eps
+--weight-decay``.
 """
 from __future__ import annotations
 
@@ -38,7 +40,8 @@ def ssgd(dnn, dataset, data_dir, nworkers, lr, batch_size, nsteps_update, max_ep
          density_warmup=True, deterministic=False, max_iters=None, compress_single_rank=False, saved_dir=".",
          bf16_shadow=True, momentum_correction=False, k_cap_factor=None, overlap=True, dump_grad_every=None,
          metrics_dir=None, f32_matmul=None, train_samples=None, checkpoint_every=2, save_final=False,
-         hip_graph=False, selection_quality_every=None):
+         hip_graph=False, selection_quality_every=None, optimizer="sgd", betas=(0.9, 0.999), adam_eps=1e-8,
+         weight_decay=None):
     rank = hvd.rank()
     device = "cpu"
     if torch.cuda.is_available():
@@ -67,7 +70,8 @@ def ssgd(dnn, dataset, data_dir, nworkers, lr, batch_size, nsteps_update, max_ep
                         data_dir=data_dir, dataset=dataset, dnn=dnn, lr=lr, nworkers=nworkers, prefix="allreduce",
                         pretrain=pretrain, num_steps=num_steps, device=device, amp=amp,
                         channels_last=channels_last, seed=rank, weights_dir=os.path.join(saved_dir, "weights"),
-                        train_samples=train_samples, checkpoint_every=checkpoint_every)
+                        train_samples=train_samples, checkpoint_every=checkpoint_every, optimizer=optimizer,
+                        betas=betas, adam_eps=adam_eps, weight_decay=weight_decay)
     init = torch.tensor([trainer.get_train_epoch(), trainer.get_train_iter()], dtype=torch.int64,
                         device=trainer.device)
     init = hvd.broadcast(init, root_rank=0)
@@ -222,6 +226,18 @@ def _finish(trainer, optimizer, save_final):
     return trainer, optimizer
 
 
+def _add_optimizer_flags(p):
+    """``--optimizer`` and its hyper-parameters (shared with train/single.py)."""
+    p.add_argument("--optimizer", type=str, default="sgd", choices=["sgd", "adam", "adamw"],
+                   help="sgd: momentum SGD (the reference); adam / adamw: torch.optim.Adam / AdamW semantics, run as "
+                        "the fused arena update with a device-side step count")
+    p.add_argument("--adam-beta1", type=float, default=0.9)
+    p.add_argument("--adam-beta2", type=float, default=0.999)
+    p.add_argument("--adam-eps", type=float, default=1e-8)
+    p.add_argument("--weight-decay", type=float, default=None,
+                   help="weight decay of the decaying group (default: the per-dataset value; AdamW: decoupled)")
+
+
 def build_parser():
     p = argparse.ArgumentParser(description="AllReduce trainer")
     p.add_argument("--batch-size", type=int, default=32)
@@ -277,6 +293,7 @@ def build_parser():
                         "device (record_occupancy, topk_overlap, energy_captured, energy_fraction and "
                         "compression_ratio_used in the metrics lines); 0 = off (default: "
                         "GKSGD_SELECTION_QUALITY_EVERY, else off)")
+    _add_optimizer_flags(p)
     p.add_argument("--save-final", action="store_true",
                    help="every rank saves its checkpoint at the end of the run (resume with --pretrain)")
     return p
@@ -316,7 +333,8 @@ def main(argv=None):
                 k_cap_factor=args.k_cap_factor, overlap=not args.no_overlap, dump_grad_every=args.dump_grad_every,
                 metrics_dir=relative_path, f32_matmul=args.f32_matmul, train_samples=args.train_samples,
                 checkpoint_every=args.checkpoint_every, save_final=args.save_final, hip_graph=args.hip_graph,
-                selection_quality_every=args.selection_quality_every)
+                selection_quality_every=args.selection_quality_every, optimizer=args.optimizer,
+                betas=(args.adam_beta1, args.adam_beta2), adam_eps=args.adam_eps, weight_decay=args.weight_decay)
 
 
 if __name__ == "__main__":

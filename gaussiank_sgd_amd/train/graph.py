@@ -4,15 +4,18 @@ Small per-GPU batches (the reference's ResNet-20 bs32 runs,
 logs/results/SGD_32_0.0001_topk) are launch-bound on MI355X: a step is a few
 hundred short kernels.  ``GraphedStep`` captures ONE complete iteration --
 forward, backward, bucket hooks -> fused Gaussian-k compression + exchange +
-decompression on the high-priority side stream, fused SGD update -- into a
+decompression on the high-priority side stream, fused SGD / Adam update -- into a
 HIP graph (``torch.cuda.CUDAGraph`` is hipGraph on ROCm) and replays it; each
 call first copies the next batch into the graph's static input buffers, so
 every replay trains on fresh data.
 
 What the graph freezes: host-side scalars read at capture time -- the
 compression density / k, momentum flags.  NOT frozen: the learning rate (the
-fused SGD kernel multiplies the captured lr by a device scalar,
-``opt._lr_mult``, refreshed from the host schedule before every replay), the
+fused SGD and Adam kernels multiply the captured lr by a device scalar,
+``opt._lr_mult``, refreshed from the host schedule before every replay),
+Adam's step count and bias corrections (the count is a device scalar that a
+one-thread launch inside the captured update increments; the update kernel
+derives 1 - beta^t from it, so replay t behaves as eager step t), the
 compressor seeds (random-k / DGC sampling read one int32 device word per
 bucket, ``opt.refresh_device_seeds``, so every replay draws new indices) and
 the dropout masks (the attention / add+LayerNorm kernels mix a per-device

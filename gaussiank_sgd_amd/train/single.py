@@ -11,7 +11,8 @@ Speed: %f images/s`` every ``display`` iterations.
 MI355X: the update is the fused one-launch SGD over the flat parameter arena
 (the ``DistributedOptimizer`` in a world of one: no hooks, no exchange) and,
 on the GPU, the convolution / linear weight gradients go straight into that
-arena; ``--plain-sgd`` keeps ``torch.optim.SGD`` as the reference did.
+arena; ``--plain-sgd`` keeps ``torch.optim.SGD`` as the reference did;
+``--optimizer adam|adamw`` runs the fused Adam / AdamW arena update instead.
 Run: ``python -m gaussiank_sgd_amd.train.single --dnn resnet20 --dataset
 cifar10`` (or ``python -m gaussiank_sgd_amd.train.trainer``).
 """
@@ -32,7 +33,8 @@ from .trainer import DLTrainer, _support_datasets, _support_dnns
 
 def train_with_single(dnn, dataset, data_dir, nworkers, lr, batch_size, nsteps_update, max_epochs, num_steps=1,
                       amp=None, channels_last=False, max_iters=None, train_samples=None, fused=True,
-                      f32_matmul=None, saved_dir="."):
+                      f32_matmul=None, saved_dir=".", optimizer="sgd", betas=(0.9, 0.999), adam_eps=1e-8,
+                      weight_decay=None):
     device = "cpu"
     if torch.cuda.is_available():
         torch.cuda.set_device(0)
@@ -43,7 +45,8 @@ def train_with_single(dnn, dataset, data_dir, nworkers, lr, batch_size, nsteps_u
     trainer = DLTrainer(0, nworkers, dist=False, batch_size=batch_size, is_weak_scaling=True, ngpus=1,
                         data_dir=data_dir, dataset=dataset, dnn=dnn, lr=lr, nworkers=nworkers, prefix="singlegpu",
                         num_steps=num_steps, device=device, amp=amp, channels_last=channels_last,
-                        weights_dir=os.path.join(saved_dir, "weights"), train_samples=train_samples)
+                        weights_dir=os.path.join(saved_dir, "weights"), train_samples=train_samples,
+                        optimizer=optimizer, betas=betas, adam_eps=adam_eps, weight_decay=weight_decay)
     if fused:
         from ..compression import compressors
         from ..parallel.distributed_optimizer import DistributedOptimizer
@@ -110,6 +113,8 @@ def build_parser():
     p.add_argument("--f32-matmul", type=str, default=os.environ.get("GKSGD_F32_MATMUL", "bf16x6"),
                    choices=["native", "bf16x6"], help="fp32 GEMM algorithm (default: %(default)s, as bench.py)")
     p.add_argument("--saved-dir", type=str, default=".")
+    from .dist_trainer import _add_optimizer_flags
+    _add_optimizer_flags(p)
     p.add_argument("--logdir-root", type=str, default="./logs")
     return p
 
@@ -128,7 +133,9 @@ def main(argv=None):
     return train_with_single(args.dnn, args.dataset, args.data_dir, 1, args.lr, args.batch_size, args.nsteps_update,
                              args.max_epochs, args.num_steps, amp=args.amp, channels_last=args.channels_last,
                              max_iters=args.max_iters, train_samples=args.train_samples, fused=not args.plain_sgd,
-                             f32_matmul=args.f32_matmul, saved_dir=args.saved_dir)
+                             f32_matmul=args.f32_matmul, saved_dir=args.saved_dir, optimizer=args.optimizer,
+                             betas=(args.adam_beta1, args.adam_beta2), adam_eps=args.adam_eps,
+                             weight_decay=args.weight_decay)
 
 
 if __name__ == "__main__":

@@ -104,7 +104,8 @@ class DLTrainer:
                  sparsity=0.95, pretrain=None, num_steps=35, tb_writer=None, amp_handle=None, device=None,
                  amp: Optional[str] = None, channels_last: bool = False, learnable_data: bool = False,
                  seed: int = 0, data_pool: int = 4, weights_dir: str = "./weights", seq_len: Optional[int] = None,
-                 train_samples: Optional[int] = None, checkpoint_every: int = 2):
+                 train_samples: Optional[int] = None, checkpoint_every: int = 2, optimizer: str = "sgd",
+                 betas=(0.9, 0.999), adam_eps: float = 1e-8, weight_decay: Optional[float] = None):
         # data_dir: real datasets (data/real.py: CIFAR-10 binary, MNIST idx, PTB text, .npz / .npy
         # arrays), sharded by (rank, nworkers); absent or unrecognised -> synthetic, shape-exact
         self.size = size
@@ -166,19 +167,30 @@ class DLTrainer:
             self.criterion = nn.CTCLoss(blank=0, reduction="sum", zero_infinity=True)
         else:
             self.criterion = nn.CrossEntropyLoss()
-        weight_decay = 1e-4
+        dataset_wd = 1e-4
         self.m = 0.9
         if dataset == "an4":
             self.lstman4_sched = schedules.AN4Schedule(lr)
         elif dataset == "ptb":
             self.m = 0
-            weight_decay = 0
+            dataset_wd = 0
         elif dataset == "imagenet":
             self.m = 0.875
-            weight_decay = 2 * 3.0517578125e-05
+            dataset_wd = 2 * 3.0517578125e-05
+        # weight_decay=None: the per-dataset value; a given value holds for every optimizer, SGD included
+        weight_decay = dataset_wd if weight_decay is None else float(weight_decay)
         self.weight_decay = weight_decay
-        self.optimizer = torch.optim.SGD(sgd_param_groups(self.net, weight_decay), lr=self.lr, momentum=self.m,
-                                         weight_decay=weight_decay, nesterov=False)
+        # the same decay / no-decay split (1-D, bn, bias) for every optimizer
+        groups = sgd_param_groups(self.net, weight_decay)
+        if optimizer == "sgd":
+            self.optimizer = torch.optim.SGD(groups, lr=self.lr, momentum=self.m, weight_decay=weight_decay,
+                                             nesterov=False)
+        elif optimizer in ("adam", "adamw"):
+            cls = torch.optim.AdamW if optimizer == "adamw" else torch.optim.Adam
+            self.optimizer = cls(groups, lr=self.lr, betas=(float(betas[0]), float(betas[1])), eps=float(adam_eps),
+                                 weight_decay=weight_decay)
+        else:
+            raise ValueError("optimizer must be 'sgd', 'adam' or 'adamw', not %r" % (optimizer,))
         self.train_epoch = 0
         self.data_prepare(learnable_data, data_pool, seq_len)
         if self.pretrain is not None and os.path.isfile(self.pretrain):
