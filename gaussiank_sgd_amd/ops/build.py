@@ -73,6 +73,7 @@ CXX_SOURCES = [
     "bindings.cpp",
 ]
 HEADERS = ["kernels/common.h", "kernels/gk_kernels.h", "kernels/mfma_util.h", "kernels/gemm_kern.h",
+           "kernels/gemm_cfg.h",
            "kernels/wino_x6_common.h",
            "comm/rccl_engine.h"]
 # per-file extra flags: the sparse aggregation must round product and sum

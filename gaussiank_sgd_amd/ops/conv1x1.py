@@ -60,15 +60,14 @@ _timings: Dict[tuple, list] = {}      # key -> [(tag, ms or error)] of the searc
 _WINO = os.environ.get("GKSGD_WINO", "1") != "0"
 _FORCE = os.environ.get("GKSGD_CONV_FORCE", "")
 _WINO_GRIDS = (0, 1 << 20)
-# candidate kernel configurations (gemm.hip: cfg digits = tile + 10*panel + 100*stages)
+# candidate kernel configurations: the digits of a cfg word are fields, see csrc/kernels/gemm_cfg.h
 _NT_CFGS = [1, 2, 3, 4, 11, 13, 21, 22, 23, 24, 111, 113, 121, 122, 123, 124, 25, 26, 27, 125, 126, 127,
             211, 212, 213, 214, 221, 222, 223, 224]   # 2xx: four LDS stages (more bytes in flight)
 # grid override: 0 = persistent (about two blocks per CU), else a fixed block count
 _NT_GRIDS = (0, 512, 1 << 20)
 _TN_CFGS = [(c, s) for c in (1, 2, 3, 4, 5, 6, 7, 8, 21, 22, 23, 24, 27, 9, 29, 101, 121, 102, 122) for s in (0, 128)]
-# fp32: 64x64 wave tiles (gemm.hip maps NT tiles 5-7 onto them) and, cfg + 1000, 32x64 wave tiles
-# (twice the waves: the small-M layers of small batches, e.g. the reference's bs32); TN cfg = tile +
-# 10 * (1: two stages)
+# fp32: 64x64 wave tiles (NT tiles 5-7 map onto them) and, cfg + 1000, 32x64 wave tiles
+# (twice the waves: the small-M layers of small batches, e.g. the reference's bs32)
 _NT_CFGS_F32 = [1, 2, 3, 4, 7, 11, 12, 13, 14, 21, 22, 23, 24, 101, 102, 103, 104, 201, 202, 203, 204,
                 1001, 1002, 1003, 1004, 1005, 1006, 1007, 1021, 1022, 1101, 1102, 1103]
 _TN_CFGS_F32 = [(c, s) for c in (1, 2, 3, 4, 5, 6, 7, 8, 9, 11, 12, 13, 14, 15, 16) for s in (0, 64)]

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "comm/rccl_engine.h"
+#include "kernels/gemm_cfg.h"
 #include "kernels/gk_kernels.h"
 
 namespace {
@@ -1229,6 +1230,36 @@ bool lazy_args(const c10::optional<at::Tensor>& x, const c10::optional<at::Tenso
   return true;
 }
 
+// What gemm_nt and conv_nt do around the gk:: call on account of the configuration word
+// (kernels/gemm_cfg.h NtWord): the split-K workspace [S, M, N] (gemm.hip
+// nt_splitk_reduce_kernel sums its planes), the B operand [N, K] (row stride ldb) of product
+// family 3 split into bf16 planes once per call, and the message of a refusal.
+struct NtWordAux {
+  at::Tensor ws, b3;
+  NtWordAux(const char* op, const gk::cfg::NtWord& w, bool gather, bool f32, bool has_lz, const at::Tensor& B,
+            int64_t ldb, int64_t M, int64_t N, int64_t K, int64_t C, hipStream_t stream) {
+    if (w.planes > 1) {
+      TORCH_CHECK(f32 && !has_lz && w.planes <= 16 && gk::cfg::splitk_divides(w.planes, gather, (int)K, (int)C), op,
+                  " split-K: fp32, no lazy operand, S <= 16 ", gather ? "dividing the K slices" : "and K % (64 S) == 0");
+      ws = at::empty({w.planes, M, N}, B.options().dtype(at::kFloat));
+    }
+    if (w.family == 3) {
+      // (a row GEMM also needs whole 32-deep slices; a convolution's C % 64 == 0 gives them)
+      TORCH_CHECK(B.scalar_type() == at::kFloat && (gather || K % 32 == 0), op, ": cfg family 3 takes fp32 operands");
+      b3 = at::empty({N, 3 * K}, B.options().dtype(at::kBFloat16));
+      gk::split3_rows(B.data_ptr<float>(), ldb, b3.data_ptr(), N, (int)K, stream);
+    }
+  }
+  float* ws_ptr() const { return ws.defined() ? ws.data_ptr<float>() : nullptr; }
+  const void* b3_ptr() const { return b3.defined() ? b3.data_ptr() : nullptr; }
+  static int64_t checked(const char* op, int r) {
+    TORCH_CHECK(r != gk::cfg::kRowGemmsOnly, op,
+                ": the register-staged bf16x6 kernels (cfg digit 200000/300000) take plain row GEMMs only");
+    TORCH_CHECK(r >= 0, op, ": the lazy operand's coefficient table does not fit this tile configuration");
+    return r;
+  }
+};
+
 int64_t gemm_nt(at::Tensor A, at::Tensor B, at::Tensor C, int64_t cfg, int64_t max_blocks,
                 c10::optional<at::Tensor> stats, c10::optional<at::Tensor> bias, c10::optional<at::Tensor> bn_h,
                 c10::optional<at::Tensor> bn_dy2, c10::optional<at::Tensor> bn_mask, c10::optional<at::Tensor> lz_x, c10::optional<at::Tensor> lz_coef,
@@ -1248,29 +1279,13 @@ int64_t gemm_nt(at::Tensor A, at::Tensor B, at::Tensor C, int64_t cfg, int64_t m
   gk::LazyArgs lz{};
   const bool has_lz = lazy_args(lz_x, lz_coef, lz_padz, lz_padx, A, K, &lz);
   c10::DeviceGuard guard(A.device());
-  // cfg digit 10000: split-K over S = (cfg / 10000) % 10 fp32 partial planes (gemm.hip nt_splitk_reduce_kernel);
-  // digit 100000: fp32 operands multiplied as bf16x6 products (gemm_kern.h X6)
-  const int64_t S = (cfg / 10000) % 10;
-  at::Tensor ws;
-  if (S > 1) {
-    TORCH_CHECK(A.scalar_type() == at::kFloat && !has_lz && S <= 16 && K % (64 * S) == 0,
-                "gemm_nt split-K: fp32, no lazy operand, S <= 16 and K % (64 S) == 0");
-    ws = at::empty({S, M, N}, A.options().dtype(at::kFloat));
-  }
-  // digit 300000: register-staged bf16x6 with B split into bf16 planes here, once per call
-  at::Tensor b3;
-  if ((cfg / 100000) % 10 == 3) {
-    TORCH_CHECK(B.scalar_type() == at::kFloat && K % 32 == 0, "gemm_nt: cfg family 3 takes fp32 operands");
-    b3 = at::empty({N, 3 * K}, B.options().dtype(at::kBFloat16));
-    gk::split3_rows(B.data_ptr<float>(), B.stride(0), b3.data_ptr(), N, (int)K, cur_stream(A));
-  }
+  const bool f32 = A.scalar_type() == at::kFloat;
+  const NtWordAux aux("gemm_nt", gk::cfg::NtWord::decode((int)cfg), false, f32, has_lz, B, B.stride(0), M, N, K, K,
+                      cur_stream(A));
   const int r = gk::gemm_nt(A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), C.data_ptr(), C.stride(0), M, (int)N,
-                            (int)K, A.scalar_type() == at::kFloat, (int)cfg, (int)max_blocks, sp, rows,
-                            bias_ptr(bias, N), has_bn ? &bn : nullptr, has_lz ? &lz : nullptr, cur_stream(A),
-                            S > 1 ? ws.data_ptr<float>() : nullptr, b3.defined() ? b3.data_ptr() : nullptr);
-  TORCH_CHECK(r != -2, "gemm_nt: the register-staged bf16x6 kernels (cfg digit 200000/300000) take plain row GEMMs only");
-  TORCH_CHECK(r >= 0, "gemm_nt: the lazy operand's coefficient table does not fit this tile configuration");
-  return r;
+                            (int)K, f32, (int)cfg, (int)max_blocks, sp, rows, bias_ptr(bias, N),
+                            has_bn ? &bn : nullptr, has_lz ? &lz : nullptr, cur_stream(A), aux.ws_ptr(), aux.b3_ptr());
+  return NtWordAux::checked("gemm_nt", r);
 }
 
 // W[N, K] += G[M, N]^T . X[M, K]   (fp32 W, float atomics)
@@ -1289,7 +1304,7 @@ void gemm_tn_acc(at::Tensor G, at::Tensor X, at::Tensor W, int64_t cfg, int64_t 
   c10::DeviceGuard guard(G.device());
   const int rc = gk::gemm_tn_acc(G.data_ptr(), G.stride(0), X.data_ptr(), X.stride(0), W.data_ptr<float>(), W.stride(0), M, (int)N,
                   (int)K, G.scalar_type() == at::kFloat, (int)cfg, (int)splits, has_lz ? &lz : nullptr, cur_stream(G));
-  TORCH_CHECK(rc != -2, "gemm_tn_acc: the register-staged bf16x6 kernels (cfg digit 200000) take plain row GEMMs only");
+  TORCH_CHECK(rc != gk::cfg::kRowGemmsOnly, "gemm_tn_acc: the register-staged bf16x6 kernels (cfg digit 200000) take plain row GEMMs only");
 }
 
 // implicit-GEMM convolution over NHWC bf16 (x: [N, C, H, W] channels-last,
@@ -1334,29 +1349,14 @@ int64_t conv_nt(at::Tensor x, at::Tensor w, at::Tensor y, at::Tensor zero, int64
   gk::LazyArgs lz{};
   const bool has_lz = lazy_args(lz_x, lz_coef, lz_padz, lz_padx, x, C, &lz);
   c10::DeviceGuard guard(x.device());
-  // cfg digit 10000: split-K over S = (cfg / 10000) % 10 fp32 partial planes of the (tap, channel) slices
-  const int64_t S = (cfg / 10000) % 10;
-  at::Tensor ws;
-  if (S > 1) {
-    TORCH_CHECK(x.scalar_type() == at::kFloat && !has_lz && S <= 16 && C % 32 == 0 && (KH * KW * C / 32) % S == 0,
-                "conv_nt split-K: fp32, no lazy operand, S <= 16 dividing the K slices");
-    ws = at::empty({S, M, Co}, x.options());
-  }
-  at::Tensor b3;
-  if ((cfg / 100000) % 10 == 3) {
-    const int64_t K = KH * KW * C;
-    TORCH_CHECK(x.scalar_type() == at::kFloat, "conv_nt: cfg family 3 takes fp32 operands");
-    b3 = at::empty({Co, 3 * K}, w.options().dtype(at::kBFloat16));
-    gk::split3_rows(w.data_ptr<float>(), K, b3.data_ptr(), Co, (int)K, cur_stream(x));
-  }
+  const bool f32 = x.scalar_type() == at::kFloat;
+  const int64_t K = KH * KW * C;
+  const NtWordAux aux("conv_nt", gk::cfg::NtWord::decode((int)cfg), true, f32, has_lz, w, K, M, Co, K, C, cur_stream(x));
   const int r = gk::conv_nt(x.data_ptr(), zero.data_ptr(), (int)H, (int)W, (int)C, (int)OH, (int)OW, (int)stride,
-                            (int)pad, (int)KH, (int)KW, w.data_ptr(), y.data_ptr(), M, (int)Co,
-                            x.scalar_type() == at::kFloat, (int)cfg, (int)max_blocks, sp, rows, bias_ptr(bias, Co),
-                            has_bn ? &bn : nullptr, has_lz ? &lz : nullptr, cur_stream(x),
-                            S > 1 ? ws.data_ptr<float>() : nullptr, b3.defined() ? b3.data_ptr() : nullptr);
-  TORCH_CHECK(r != -2, "conv_nt: the register-staged bf16x6 kernels (cfg digit 200000/300000) take plain row GEMMs only");
-  TORCH_CHECK(r >= 0, "conv_nt: the lazy operand's coefficient table does not fit this tile configuration");
-  return r;
+                            (int)pad, (int)KH, (int)KW, w.data_ptr(), y.data_ptr(), M, (int)Co, f32, (int)cfg,
+                            (int)max_blocks, sp, rows, bias_ptr(bias, Co), has_bn ? &bn : nullptr,
+                            has_lz ? &lz : nullptr, cur_stream(x), aux.ws_ptr(), aux.b3_ptr());
+  return NtWordAux::checked("conv_nt", r);
 }
 
 // Winograd F(2x2, 3x3) fp32 convolution (winograd.hip).  w: forward weight
@@ -1619,7 +1619,7 @@ void conv_tn_acc(at::Tensor dy, at::Tensor x, at::Tensor wout, at::Tensor zero, 
   const int rc = gk::conv_tn_acc(dy.data_ptr(), x.data_ptr(), zero.data_ptr(), (int)H, (int)W, (int)C, (int)OH, (int)OW,
                   (int)stride, (int)pad, (int)KH, (int)KW, wout.data_ptr<float>(), M, (int)Co,
                   x.scalar_type() == at::kFloat, (int)cfg, (int)splits, has_lz ? &lz : nullptr, cur_stream(x));
-  TORCH_CHECK(rc != -2, "conv_tn_acc: the register-staged bf16x6 kernels (cfg digit 200000) take plain row GEMMs only");
+  TORCH_CHECK(rc != gk::cfg::kRowGemmsOnly, "conv_tn_acc: the register-staged bf16x6 kernels (cfg digit 200000) take plain row GEMMs only");
 }
 
 // fused residual add (+ dropout) + LayerNorm (ln.hip)

@@ -26,54 +26,24 @@
 //   transpose read: 4 rows x 16 columns of 16-bit data delivered column-wise).
 //   Each block reduces a contiguous slice of M for one output tile and adds
 //   its fp32 partial into the (gradient-arena) output with float atomics.
+#include "gemm_cfg.h"
 #include "gemm_kern.h"
 
 namespace gk {
 
-static int nt_unit_b16(bool gather, GK_NT_UNIT_ARGS) {
-  return gather ? nt_b16_gat(GK_NT_UNIT_PASS) : nt_b16_row(GK_NT_UNIT_PASS);
-}
-
-// fp32 operands: cfg digit 100000 selects the bf16x6 products (gemm_kern.h X6)
-static int nt_unit_f32(bool gather, GK_NT_UNIT_ARGS) {
-  const int fam = (cfg / 100000) % 10;
-  if (fam == 2 || fam == 3) {
-    // bf16x6 with register staging: row GEMMs and stride / padding implicit
-    // GEMMs (C a multiple of 32) without a lazy operand, split-K or remap;
-    // family 3: B pre-split (geo.b3, the binding's split3_rows)
-    if (lza || geo.KZ > 1 || geo.RH || (fam == 3) != (geo.b3 != nullptr)) return -2;
-    if (gather) {
-      // 32-bit element offsets into x (gemm_kern.h x62 gather)
-      const int64_t nimg = M / ((int64_t)geo.OH * geo.OW);
-      if (geo.C % 32 != 0 || nimg * geo.H * geo.W * geo.C >= ((int64_t)1 << 31)) return -2;
-      return nt_x62_gat(static_cast<const float*>(A), static_cast<const float*>(B), static_cast<float*>(C), M, N, K,
-                        cfg % 100000, max_blocks, geo, stats, stats_ld, stats_rows, bb, stream);
-    }
-    return nt_x62_row(static_cast<const float*>(A), lda, static_cast<const float*>(B), ldb, static_cast<float*>(C),
-                      ldc, M, N, K, cfg % 100000, max_blocks, geo.bias, stats, stats_ld, stats_rows, bb, geo.b3, stream);
+// one NT GEMM on the instantiation unit its plan names (gemm_cfg.h nt_plan)
+static int nt_unit(cfg::Unit unit, bool gather, GK_NT_UNIT_ARGS) {
+  switch (unit) {
+    case cfg::Unit::b16: return gather ? nt_b16_gat(GK_NT_UNIT_PASS) : nt_b16_row(GK_NT_UNIT_PASS);
+    case cfg::Unit::x6: return gather ? nt_x6_gat(GK_NT_UNIT_PASS) : nt_x6_row(GK_NT_UNIT_PASS);
+    case cfg::Unit::x62:
+      if (gather)
+        return nt_x62_gat(static_cast<const float*>(A), static_cast<const float*>(B), static_cast<float*>(C), M, N, K,
+                          w, max_blocks, geo, stats, stats_ld, stats_rows, bb, stream);
+      return nt_x62_row(static_cast<const float*>(A), lda, static_cast<const float*>(B), ldb, static_cast<float*>(C),
+                        ldc, M, N, K, w, max_blocks, geo.bias, stats, stats_ld, stats_rows, bb, geo.b3, stream);
+    default: return gather ? nt_f32_gat(GK_NT_UNIT_PASS) : nt_f32_row(GK_NT_UNIT_PASS);
   }
-  const bool x6 = (cfg / 100000) % 10 == 1;
-  cfg %= 100000;
-  if (x6) return gather ? nt_x6_gat(GK_NT_UNIT_PASS) : nt_x6_row(GK_NT_UNIT_PASS);
-  return gather ? nt_f32_gat(GK_NT_UNIT_PASS) : nt_f32_row(GK_NT_UNIT_PASS);
-}
-
-// fp32 grad-weight: cfg digit 100000 selects the bf16x6 products
-// (digit 200000: register-staged bf16x6, plain row form only; -2 = refused)
-static int tn_unit_f32x(bool gather, const float* G, int64_t ldg, const float* X, int64_t ldx, float* W, int64_t ldw,
-                        int64_t M, int N, int K, int cfg, int splits, const ConvGeo& geo, const LazyArgs* lza,
-                        hipStream_t stream) {
-  const int fam = (cfg / 100000) % 10;
-  if (fam == 3) return -2;   // pre-split B: forward / grad-input kernels only
-  if (fam == 2) {
-    if (gather || lza) return -2;
-    tn_x62_row(G, ldg, X, ldx, W, ldw, M, N, K, cfg % 100000, splits, stream);
-  } else if (fam == 1) {
-    tn_unit_x6(gather, G, ldg, X, ldx, W, ldw, M, N, K, cfg % 100000, splits, geo, lza, stream);
-  } else {
-    tn_unit_f32(gather, G, ldg, X, ldx, W, ldw, M, N, K, cfg % 100000, splits, geo, lza, stream);
-  }
-  return 0;
 }
 
 // fp32 [R, S] (row stride ld) -> three bf16 planes [R][S / 32][3][32] (the B
@@ -187,29 +157,43 @@ int splitk_reduce(const float* ws, int S, int64_t M, int N, float* C, int64_t ld
   return (int)gx;
 }
 
+// An NT call as the configuration word's plan says: refused, one GEMM on its
+// unit, or split-K -- KZ plain partial planes into splitk_ws [S][M][N] (over
+// the K slices; an implicit GEMM's (tap, channel) slices), then the reduce
+// epilogue with the bias, statistics or BN-backward of the fused kernel.
+static int nt_run(bool f32, bool gather, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
+                  int64_t M, int N, int K, int cfg_word, int max_blocks, const ConvGeo& g, float* stats, int stats_rows,
+                  const BnBwdArgs* bn, const LazyArgs* lazy, float* splitk_ws, hipStream_t stream) {
+  const cfg::NtWord w = cfg::NtWord::decode(cfg_word);
+  if (!f32) lazy = nullptr;
+  // elements of the gathered operand: the x62 gather kernels index it with 32 bits
+  const int64_t x_elems = gather ? M / ((int64_t)g.OH * g.OW) * g.H * g.W * g.C : 0;
+  const cfg::NtPlan p = cfg::nt_plan(w, f32, gather, lazy != nullptr, g.b3 != nullptr, g.RH != 0, splitk_ws != nullptr, K,
+                                     g.C, x_elems);
+  if (p.status < 0) return p.status;
+  if (p.planes > 1) {
+    ConvGeo gz = g;
+    gz.bias = nullptr;
+    gz.b3 = nullptr;
+    gz.KZ = p.planes;
+    const int r = nt_unit(p.unit, gather, A, lda, B, ldb, splitk_ws, N, M, N, K / p.planes, w, max_blocks, gz, nullptr, 0,
+                          0, BnBwd{}, nullptr, stream);
+    if (r < 0) return r;
+    return splitk_reduce(splitk_ws, p.planes, M, N, static_cast<float*>(C), ldc, g.bias, stats, stats_rows, bn, stream);
+  }
+  const BnBwd bb = bn ? BnBwd{bn->h, bn->dy2, bn->mask} : BnBwd{};
+  return nt_unit(p.unit, gather, A, lda, B, ldb, C, ldc, M, N, K, w, max_blocks, g, stats, (int64_t)stats_rows * N,
+                 stats_rows, bb, lazy, stream);
+}
+
 int gemm_nt(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int64_t M, int N, int K,
             bool f32, int cfg, int max_blocks, float* stats, int stats_rows, const float* bias, const BnBwdArgs* bn,
             const LazyArgs* lazy, hipStream_t stream, float* splitk_ws, const void* b3) {
   ConvGeo g{};
   g.bias = bias;
   g.b3 = static_cast<const uint16_t*>(b3);
-  const BnBwd bb = bn ? BnBwd{bn->h, bn->dy2, bn->mask} : BnBwd{};
-  const int64_t sld = (int64_t)stats_rows * N;
-  const int S = (cfg / 10000) % 10;
-  const int x6 = cfg / 100000 * 100000;   // bf16x6 digit, kept for the split-K planes
-  if (S > 1) {
-    // split-K (fp32 row GEMM, host-checked: K % (64 S) == 0, no lazy operand):
-    // KZ plain partial planes into splitk_ws [S][M][N], then the reduce epilogue
-    if (!f32 || lazy || splitk_ws == nullptr || K % (64 * S) != 0) return -1;
-    ConvGeo gz{};
-    gz.KZ = S;
-    const int r = nt_unit_f32(false, A, lda, B, ldb, splitk_ws, N, M, N, K / S, x6 + cfg % 10000, max_blocks, gz,
-                                            nullptr, 0, 0, BnBwd{}, nullptr, stream);
-    if (r < 0) return r;
-    return splitk_reduce(splitk_ws, S, M, N, static_cast<float*>(C), ldc, bias, stats, stats_rows, bn, stream);
-  }
-  return f32 ? nt_unit_f32(false, A, lda, B, ldb, C, ldc, M, N, K, cfg, max_blocks, g, stats, sld, stats_rows, bb, lazy, stream)
-             : nt_unit_b16(false, A, lda, B, ldb, C, ldc, M, N, K, cfg, max_blocks, g, stats, sld, stats_rows, bb, nullptr, stream);
+  return nt_run(f32, false, A, lda, B, ldb, C, ldc, M, N, K, cfg, max_blocks, g, stats, stats_rows, bn, lazy, splitk_ws,
+                stream);
 }
 
 int conv_nt(const void* X, const void* zero, int H, int W, int C, int OH, int OW, int S, int P, int KH, int KW,
@@ -218,23 +202,7 @@ int conv_nt(const void* X, const void* zero, int H, int W, int C, int OH, int OW
   ConvGeo g{zero, H, W, C, OH, OW, S, P, KW, bias};
   g.b3 = static_cast<const uint16_t*>(b3);
   const int K = KH * KW * C;
-  const int SK = (cfg / 10000) % 10;
-  const int x6 = cfg / 100000 * 100000;
-  if (SK > 1) {
-    // split-K over the (tap, channel) slices: plain partial planes, then the reduce epilogue
-    const int nks = K / 32;   // fp32 K slices
-    if (!f32 || lazy || splitk_ws == nullptr || nks % SK != 0 || C % 32 != 0) return -1;
-    ConvGeo gz{zero, H, W, C, OH, OW, S, P, KW, nullptr};
-    gz.KZ = SK;
-    const int r = nt_unit_f32(true, X, C, B, K, splitk_ws, N, M, N, K / SK, x6 + cfg % 10000, max_blocks, gz,
-                                           nullptr, 0, 0, BnBwd{}, nullptr, stream);
-    if (r < 0) return r;
-    return splitk_reduce(splitk_ws, SK, M, N, static_cast<float*>(Y), N, bias, stats, stats_rows, bn, stream);
-  }
-  const BnBwd bb = bn ? BnBwd{bn->h, bn->dy2, bn->mask} : BnBwd{};
-  const int64_t sld = (int64_t)stats_rows * N;
-  return f32 ? nt_unit_f32(true, X, C, B, K, Y, N, M, N, K, cfg, max_blocks, g, stats, sld, stats_rows, bb, lazy, stream)
-             : nt_unit_b16(true, X, C, B, K, Y, N, M, N, K, cfg, max_blocks, g, stats, sld, stats_rows, bb, nullptr, stream);
+  return nt_run(f32, true, X, C, B, K, Y, N, M, N, K, cfg, max_blocks, g, stats, stats_rows, bn, lazy, splitk_ws, stream);
 }
 
 int conv_nt_remap(const void* X, int64_t ldx, const void* zero, int H, int W, int C, int OH, int OW, int KH, int KW,
@@ -242,21 +210,34 @@ int conv_nt_remap(const void* X, int64_t ldx, const void* zero, int H, int W, in
                   int max_blocks, const LazyArgs* lazy, hipStream_t stream) {
   ConvGeo g{zero, H, W, C, OH, OW, 1, 0, KW, nullptr, RH, RW, RA, RB, RZ};
   const int K = KH * KW * C;
-  if (KH * KW == 1) {   // one tap at the class pixel itself: the plain row GEMM
-    return f32 ? nt_unit_f32(false, X, ldx, B, K, Y, N, M, N, K, cfg, max_blocks, g, nullptr, 0, 0, BnBwd{}, lazy, stream)
-               : nt_unit_b16(false, X, ldx, B, K, Y, N, M, N, K, cfg, max_blocks, g, nullptr, 0, 0, BnBwd{}, nullptr, stream);
+  // one tap at the class pixel itself: the plain row GEMM
+  const bool gather = KH * KW != 1;
+  return nt_run(f32, gather, X, gather ? C : ldx, B, K, Y, N, M, N, K, cfg, max_blocks, g, nullptr, 0, nullptr, lazy,
+                nullptr, stream);
+}
+
+// a grad-weight call on the unit its configuration word names, or the refusal
+static int tn_run(bool f32, bool gather, const void* G, int64_t ldg, const void* X, int64_t ldx, float* W, int64_t ldw,
+                  int64_t M, int N, int K, int cfg_word, int splits, const ConvGeo& geo, const LazyArgs* lazy,
+                  hipStream_t stream) {
+  if (!f32) {
+    tn_unit_b16(gather, G, ldg, X, ldx, W, ldw, M, N, K, cfg::TnWord::decode(cfg_word), splits, geo, stream);
+    return 0;
   }
-  return f32 ? nt_unit_f32(true, X, C, B, K, Y, N, M, N, K, cfg, max_blocks, g, nullptr, 0, 0, BnBwd{}, lazy, stream)
-             : nt_unit_b16(true, X, C, B, K, Y, N, M, N, K, cfg, max_blocks, g, nullptr, 0, 0, BnBwd{}, nullptr, stream);
+  const cfg::TnF32Word w = cfg::TnF32Word::decode(cfg_word);
+  const cfg::TnPlan p = cfg::tn_plan(w, gather, lazy != nullptr);
+  if (p.status < 0) return p.status;
+  auto g = static_cast<const float*>(G);
+  auto x = static_cast<const float*>(X);
+  if (p.unit == cfg::Unit::x62) tn_x62_row(g, ldg, x, ldx, W, ldw, M, N, K, w, splits, stream);
+  else if (p.unit == cfg::Unit::x6) tn_unit_x6(gather, g, ldg, x, ldx, W, ldw, M, N, K, w, splits, geo, lazy, stream);
+  else tn_unit_f32(gather, g, ldg, x, ldx, W, ldw, M, N, K, w, splits, geo, lazy, stream);
+  return 0;
 }
 
 int gemm_tn_acc(const void* G, int64_t ldg, const void* X, int64_t ldx, float* W, int64_t ldw, int64_t M, int N,
                  int K, bool f32, int cfg, int splits, const LazyArgs* lazy, hipStream_t stream) {
-  if (f32)
-    return tn_unit_f32x(false, static_cast<const float*>(G), ldg, static_cast<const float*>(X), ldx, W, ldw, M, N, K, cfg,
-                           splits, ConvGeo{}, lazy, stream);
-  tn_unit_b16(false, G, ldg, X, ldx, W, ldw, M, N, K, cfg, splits, ConvGeo{}, stream);
-  return 0;
+  return tn_run(f32, false, G, ldg, X, ldx, W, ldw, M, N, K, cfg, splits, ConvGeo{}, lazy, stream);
 }
 
 int conv_tn_acc(const void* G, const void* X, const void* zero, int H, int W_, int C, int OH, int OW, int S, int P,
@@ -264,11 +245,7 @@ int conv_tn_acc(const void* G, const void* X, const void* zero, int H, int W_, i
                  hipStream_t stream) {
   ConvGeo g{zero, H, W_, C, OH, OW, S, P, KW, nullptr};
   const int K = KH * KW * C;
-  if (f32)
-    return tn_unit_f32x(true, static_cast<const float*>(G), N, static_cast<const float*>(X), C, Wout, K, M, N, K, cfg,
-                          splits, g, lazy, stream);
-  tn_unit_b16(true, G, N, X, C, Wout, K, M, N, K, cfg, splits, g, stream);
-  return 0;
+  return tn_run(f32, true, G, N, X, C, Wout, K, M, N, K, cfg, splits, g, lazy, stream);
 }
 
 }  // namespace gk

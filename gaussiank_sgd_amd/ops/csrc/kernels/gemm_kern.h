@@ -46,6 +46,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "gemm_cfg.h"
 #include "gk_kernels.h"
 #include "mfma_util.h"
 namespace gk {
@@ -106,12 +107,13 @@ struct LazyA {
   int C;                  // channels of dz (coefficient table length)
 };
 
-// per-unit dispatchers (gemm_inst.hip, one object per GK_GEMM_UNIT)
-#define GK_NT_UNIT_ARGS                                                                                      \
-  const void *A, int64_t lda, const void *B, int64_t ldb, void *C, int64_t ldc, int64_t M, int N, int K, int cfg, \
-      int max_blocks, const ConvGeo &geo, float *stats, int64_t stats_ld, int stats_rows, const BnBwd &bb,      \
-      const LazyArgs *lza, hipStream_t stream
-#define GK_NT_UNIT_PASS A, lda, B, ldb, C, ldc, M, N, K, cfg, max_blocks, geo, stats, stats_ld, stats_rows, bb, lza, stream
+// per-unit dispatchers (gemm_inst.hip, one object per GK_GEMM_UNIT); w: the decoded
+// configuration word (gemm_cfg.h) -- nothing below the gk:: entry points sees the integer
+#define GK_NT_UNIT_ARGS                                                                                  \
+  const void *A, int64_t lda, const void *B, int64_t ldb, void *C, int64_t ldc, int64_t M, int N, int K, \
+      const cfg::NtWord &w, int max_blocks, const ConvGeo &geo, float *stats, int64_t stats_ld,         \
+      int stats_rows, const BnBwd &bb, const LazyArgs *lza, hipStream_t stream
+#define GK_NT_UNIT_PASS A, lda, B, ldb, C, ldc, M, N, K, w, max_blocks, geo, stats, stats_ld, stats_rows, bb, lza, stream
 int nt_b16_row(GK_NT_UNIT_ARGS);   // unit 0
 int nt_b16_gat(GK_NT_UNIT_ARGS);   // unit 1
 int nt_f32_row(GK_NT_UNIT_ARGS);   // unit 2
@@ -120,24 +122,24 @@ int nt_x6_row(GK_NT_UNIT_ARGS);    // unit 5: fp32 operands, bf16x6 products
 int nt_x6_gat(GK_NT_UNIT_ARGS);    // unit 6
 // unit 8: fp32 row GEMMs, bf16x6 with register staging (gemm_nt_x62_kernel)
 int nt_x62_row(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M, int N, int K,
-               int cfg, int max_blocks, const float* bias, float* stats, int64_t stats_ld, int stats_rows,
+               const cfg::NtWord& w, int max_blocks, const float* bias, float* stats, int64_t stats_ld, int stats_rows,
                const BnBwd& bb, const uint16_t* b3, hipStream_t stream);
 // unit 10: implicit-GEMM convolutions, bf16x6 with register staging
-int nt_x62_gat(const float* A, const float* B, float* C, int64_t M, int N, int K, int cfg, int max_blocks,
+int nt_x62_gat(const float* A, const float* B, float* C, int64_t M, int N, int K, const cfg::NtWord& w, int max_blocks,
                const ConvGeo& geo, float* stats, int64_t stats_ld, int stats_rows, const BnBwd& bb,
                hipStream_t stream);
 // unit 9: fp32 row grad-weight GEMMs, bf16x6 with register staging (gemm_tn_x62_kernel)
 void tn_x62_row(const float* G, int64_t ldg, const float* X, int64_t ldx, float* W, int64_t ldw, int64_t M, int N,
-                int K, int cfg, int splits, hipStream_t stream);
+                int K, const cfg::TnF32Word& w, int splits, hipStream_t stream);
 // unit 7: fp32 grad-weight (TN) GEMMs with bf16x6 products
 void tn_unit_x6(bool gather, const float* G, int64_t ldg, const float* X, int64_t ldx, float* W, int64_t ldw,
-                int64_t M, int N, int K, int cfg, int splits, const ConvGeo& geo, const LazyArgs* lza,
+                int64_t M, int N, int K, const cfg::TnF32Word& w, int splits, const ConvGeo& geo, const LazyArgs* lza,
                 hipStream_t stream);
 // unit 4: grad-weight (TN) GEMMs, both operand types and forms
 void tn_unit_b16(bool gather, const void* G, int64_t ldg, const void* X, int64_t ldx, float* W, int64_t ldw, int64_t M,
-                 int N, int K, int cfg, int splits, const ConvGeo& geo, hipStream_t stream);
+                 int N, int K, const cfg::TnWord& w, int splits, const ConvGeo& geo, hipStream_t stream);
 void tn_unit_f32(bool gather, const float* G, int64_t ldg, const float* X, int64_t ldx, float* W, int64_t ldw,
-                 int64_t M, int N, int K, int cfg, int splits, const ConvGeo& geo, const LazyArgs* lza,
+                 int64_t M, int N, int K, const cfg::TnF32Word& w, int splits, const ConvGeo& geo, const LazyArgs* lza,
                  hipStream_t stream);
 
 namespace {
@@ -1036,7 +1038,7 @@ int launch_nt_any(const T* A, int64_t lda, const T* B, int64_t ldb, T* C, int64_
   }
   if constexpr (CS::NS3_OK)
     if (ns != 2 && CS::lds_bytes(K, 3, cc) <= L) return GK_NT(false, 3);
-  if (CS::lds_bytes(K, 2, cc) > L) return -1;   // does not fit (lazy coefficient table too large)
+  if (CS::lds_bytes(K, 2, cc) > L) return cfg::kDoesNotFit;   // lazy coefficient table too large
   return GK_NT(false, 2);
 #undef GK_NT
 }
@@ -1679,50 +1681,40 @@ void launch_tn_f32(const float* G, int64_t ldg, const float* X, int64_t ldx, flo
                      X, ldx, W, ldw, M, rows, geo, lz);
 }
 
+// Reaches the instantiations that cfg::tn_f32_select can name (gemm_cfg.h: tiles, fallbacks);
+// a three-stage request is kept where the tile's LDS fits.
 template <bool GATHER, bool X6 = false>
 void tn_f32_dispatch(const float* G, int64_t ldg, const float* X, int64_t ldx, float* W, int64_t ldw, int64_t M, int N,
-                     int K, int cfg, int splits, const ConvGeo& geo, const LazyArgs* lza, hipStream_t stream) {
-  // cfg = tile + 10 * stages (0/2: three, 1: two).  tiles (WN, WK), 64x64 per wave:
-  // 1 (1,1)  2 (2,1)  3 (1,2)  4 (2,2)  5 (4,1)  6 (1,4)  7 (4,2)  8 (2,4)  9 (4,4, two stages)
-  const bool ns3 = (cfg / 10) % 10 != 1;
-  cfg %= 10;
-  if (cfg <= 0) cfg = (N % 128 == 0 && K % 128 == 0) ? 4 : (N % 128 == 0 ? 2 : (K % 128 == 0 ? 3 : 1));
-  static const int cfg_bn[10] = {64, 64, 128, 64, 128, 256, 64, 256, 128, 256};
-  static const int cfg_bk[10] = {64, 64, 64, 128, 128, 64, 256, 128, 256, 256};
-  if (N % cfg_bn[cfg] != 0 || K % cfg_bk[cfg] != 0) cfg = 1;
+                     int K, const cfg::TnF32Word& w, int splits, const ConvGeo& geo, const LazyArgs* lza,
+                     hipStream_t stream) {
+  const cfg::TnF32Sel s = cfg::tn_f32_select(w, N, K, lza != nullptr);
+  const bool ns3 = s.stages == 3;
   const LazyA lz = lza ? LazyA{lza->x, lza->coef, lza->padz, lza->padx, lza->C} : LazyA{};
-#define GK_TNF(WN_, WK_)                                                                                      \
-  do {                                                                                                        \
-    if (lza) {                                                                                                \
-      if (ns3 && TnF32Cfg<WN_, WK_, 3, true>::LDS <= 160 * 1024)                                              \
-        launch_tn_f32<WN_, WK_, 3, GATHER, true, X6>(G, ldg, X, ldx, W, ldw, M, N, K, splits, geo, lz, stream);   \
-      else                                                                                                    \
-        launch_tn_f32<WN_, WK_, 2, GATHER, true, X6>(G, ldg, X, ldx, W, ldw, M, N, K, splits, geo, lz, stream);   \
-    } else if (ns3 && TnF32Cfg<WN_, WK_, 3>::LDS <= 160 * 1024)                                               \
-      launch_tn_f32<WN_, WK_, 3, GATHER, false, X6>(G, ldg, X, ldx, W, ldw, M, N, K, splits, geo, lz, stream);           \
-    else                                                                                                      \
-      launch_tn_f32<WN_, WK_, 2, GATHER, false, X6>(G, ldg, X, ldx, W, ldw, M, N, K, splits, geo, lz, stream);           \
+#define GK_TNL(WN_, WK_, LZ_)                                                                                   \
+  do {                                                                                                          \
+    if (ns3 && TnF32Cfg<WN_, WK_, 3, LZ_>::LDS <= 160 * 1024)                                                   \
+      launch_tn_f32<WN_, WK_, 3, GATHER, LZ_, X6>(G, ldg, X, ldx, W, ldw, M, N, K, splits, geo, lz, stream);     \
+    else                                                                                                        \
+      launch_tn_f32<WN_, WK_, 2, GATHER, LZ_, X6>(G, ldg, X, ldx, W, ldw, M, N, K, splits, geo, lz, stream);     \
   } while (0)
-  switch (cfg) {
-    case 2: GK_TNF(2, 1); break;
-    case 3: GK_TNF(1, 2); break;
-    case 4: GK_TNF(2, 2); break;
-    case 5: GK_TNF(4, 1); break;
-    case 6: GK_TNF(1, 4); break;
-    case 7: GK_TNF(4, 2); break;
-    case 8: GK_TNF(2, 4); break;
-    case 9:
-      if (lza) {
-        GK_TNF(2, 4);   // the lazy 256x256 tile does not fit in LDS
-      } else if (ns3 && TnF32Cfg<4, 4, 3>::LDS <= 160 * 1024) {
-        launch_tn_f32<4, 4, 3, GATHER, false, X6>(G, ldg, X, ldx, W, ldw, M, N, K, splits, geo, lz, stream);
-      } else {
-        launch_tn_f32<4, 4, 2, GATHER, false, X6>(G, ldg, X, ldx, W, ldw, M, N, K, splits, geo, lz, stream);
-      }
-      break;
-    default: GK_TNF(1, 1); break;
+#define GK_TNF(WN_, WK_)              \
+  case cfg::tn_f32_key(WN_, WK_):     \
+    if (s.lz) GK_TNL(WN_, WK_, true); \
+    else GK_TNL(WN_, WK_, false);     \
+    break
+  switch (cfg::tn_f32_key(s.wn, s.wk)) {
+    GK_TNF(2, 1);
+    GK_TNF(1, 2);
+    GK_TNF(2, 2);
+    GK_TNF(4, 1);
+    GK_TNF(1, 4);
+    GK_TNF(4, 2);
+    GK_TNF(2, 4);
+    case cfg::tn_f32_key(4, 4): GK_TNL(4, 4, false); break;   // no lazy 256x256 tile: it does not fit in LDS
+    GK_TNF(1, 1);
   }
 #undef GK_TNF
+#undef GK_TNL
 }
 
 // --------------------------------------------------------------------------
@@ -2152,38 +2144,34 @@ int launch_nt_x62(const float* A, int64_t lda, const float* B, int64_t ldb, floa
   return (int)gx;
 }
 
-// cfg % 10: tile (WM, WN) of 64x64 wave tiles: 1 (2,2) 128x128, 2 (2,4) 128x256, 3 (4,2) 256x128,
-// 4 (1,4) 64x256, 5 (4,1) 256x64, 6 (1,2) 64x128, 7 (2,1) 128x64
+// Reaches the instantiations that cfg::nt_x62_select can name (gemm_cfg.h: tiles, fallbacks).
+// (two register sets in flight, NPF 2, measured slower everywhere: no longer instantiated)
 template <bool GATHER>
 int nt_x62_dispatch(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M,
-                    int N, int K, int cfg, int max_blocks, const float* bias, float* stats, int64_t stats_ld,
-                    int stats_rows, const BnBwd& bb, const ConvGeo& geo, hipStream_t stream) {
-  static const int cfg_bn[8] = {128, 128, 256, 128, 256, 64, 128, 64};
-  cfg %= 10;
-  if (cfg < 1 || cfg > 7 || N % cfg_bn[cfg] != 0) cfg = N % 128 == 0 ? 1 : 7;
-  if (N % cfg_bn[cfg] != 0) cfg = 5;
+                    int N, int K, const cfg::NtWord& w, int max_blocks, const float* bias, float* stats,
+                    int64_t stats_ld, int stats_rows, const BnBwd& bb, const ConvGeo& geo, hipStream_t stream) {
+  const cfg::X62NtSel s = cfg::nt_x62_select(w, N, geo.b3 != nullptr, bb.h != nullptr);
 #define GK_X62N(WM_, WN_, P3_)                                                                                      \
-  return bb.h ? launch_nt_x62<WM_, WN_, true, 1, GATHER, P3_>(A, lda, B, ldb, C, ldc, M, N, K, max_blocks, bias, stats, \
-                                                              stats_ld, stats_rows, bb, geo, stream)                  \
-              : launch_nt_x62<WM_, WN_, false, 1, GATHER, P3_>(A, lda, B, ldb, C, ldc, M, N, K, max_blocks, bias,     \
-                                                               stats, stats_ld, stats_rows, bb, geo, stream)
-  // (two register sets in flight, cfg digit 10, measured slower everywhere: no longer instantiated)
-#define GK_X62(WM_, WN_)                  \
-  do {                                    \
-    if (geo.b3) GK_X62N(WM_, WN_, true);  \
-    GK_X62N(WM_, WN_, false);             \
-  } while (0)
-  switch (cfg) {
-    case 2: GK_X62(2, 4);
-    case 3: GK_X62(4, 2);
-    case 4: GK_X62(1, 4);
-    case 5: GK_X62(4, 1);
-    case 6: GK_X62(1, 2);
-    case 7: GK_X62(2, 1);
-    default: GK_X62(2, 2);
+  return s.bnb ? launch_nt_x62<WM_, WN_, true, 1, GATHER, P3_>(A, lda, B, ldb, C, ldc, M, N, K, max_blocks, bias, stats, \
+                                                               stats_ld, stats_rows, bb, geo, stream)                  \
+               : launch_nt_x62<WM_, WN_, false, 1, GATHER, P3_>(A, lda, B, ldb, C, ldc, M, N, K, max_blocks, bias,     \
+                                                                stats, stats_ld, stats_rows, bb, geo, stream)
+#define GK_X62(WM_, WN_)               \
+  case cfg::x62_key(WM_, WN_):         \
+    if (s.p3) GK_X62N(WM_, WN_, true); \
+    GK_X62N(WM_, WN_, false)
+  switch (cfg::x62_key(s.wm, s.wn)) {
+    GK_X62(2, 4);
+    GK_X62(4, 2);
+    GK_X62(1, 4);
+    GK_X62(4, 1);
+    GK_X62(1, 2);
+    GK_X62(2, 1);
+    GK_X62(2, 2);
   }
 #undef GK_X62
 #undef GK_X62N
+  return cfg::kDoesNotFit;   // not reached: nt_x62_select names instantiated tiles only
 }
 
 // --------------------------------------------------------------------------
@@ -2383,134 +2371,93 @@ void launch_tn_x62(const float* G, int64_t ldg, const float* X, int64_t ldx, flo
                      dim3(Cfg::THREADS), Cfg::LDS, stream, G, ldg, X, ldx, W, ldw, M, rows);
 }
 
-// cfg % 10: tile (WN, WK) of 64x64 wave tiles: 1 (1,1) 64x64  2 (2,1) 128x64  3 (1,2) 64x128  4 (2,2) 128x128
-// 5 (4,1) 256x64  6 (1,4) 64x256  7 (4,2) 256x128  8 (2,4) 128x256
+// Reaches the instantiations that cfg::tn_x62_select can name (gemm_cfg.h: tiles, fallbacks).
 inline void tn_x62_dispatch(const float* G, int64_t ldg, const float* X, int64_t ldx, float* W, int64_t ldw, int64_t M,
-                            int N, int K, int cfg, int splits, hipStream_t stream) {
-  static const int cfg_bn[9] = {64, 64, 128, 64, 128, 256, 64, 256, 128};
-  static const int cfg_bk[9] = {64, 64, 64, 128, 128, 64, 256, 128, 256};
-  cfg %= 10;
-  if (cfg < 1 || cfg > 8 || N % cfg_bn[cfg] != 0 || K % cfg_bk[cfg] != 0) cfg = 1;
-  switch (cfg) {
-    case 2: launch_tn_x62<2, 1>(G, ldg, X, ldx, W, ldw, M, N, K, splits, stream); break;
-    case 3: launch_tn_x62<1, 2>(G, ldg, X, ldx, W, ldw, M, N, K, splits, stream); break;
-    case 4: launch_tn_x62<2, 2>(G, ldg, X, ldx, W, ldw, M, N, K, splits, stream); break;
-    case 5: launch_tn_x62<4, 1>(G, ldg, X, ldx, W, ldw, M, N, K, splits, stream); break;
-    case 6: launch_tn_x62<1, 4>(G, ldg, X, ldx, W, ldw, M, N, K, splits, stream); break;
-    case 7: launch_tn_x62<4, 2>(G, ldg, X, ldx, W, ldw, M, N, K, splits, stream); break;
-    case 8: launch_tn_x62<2, 4>(G, ldg, X, ldx, W, ldw, M, N, K, splits, stream); break;
-    default: launch_tn_x62<1, 1>(G, ldg, X, ldx, W, ldw, M, N, K, splits, stream); break;
+                            int N, int K, const cfg::TnF32Word& w, int splits, hipStream_t stream) {
+  const cfg::X62TnSel s = cfg::tn_x62_select(w, N, K);
+#define GK_TX62(WN_, WK_)        \
+  case cfg::x62_key(WN_, WK_):   \
+    launch_tn_x62<WN_, WK_>(G, ldg, X, ldx, W, ldw, M, N, K, splits, stream); \
+    break
+  switch (cfg::x62_key(s.wn, s.wk)) {
+    GK_TX62(2, 1);
+    GK_TX62(1, 2);
+    GK_TX62(2, 2);
+    GK_TX62(4, 1);
+    GK_TX62(1, 4);
+    GK_TX62(4, 2);
+    GK_TX62(2, 4);
+    GK_TX62(1, 1);
   }
+#undef GK_TX62
 }
 
+// Reaches the instantiations that cfg::nt_select can name; the tile tables and the
+// fallback rules are in gemm_cfg.h.
 template <bool GATHER, typename T, bool X6 = false>
-int nt_dispatch(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int64_t M, int N,
-                int K, int cfg, int max_blocks, const ConvGeo& geo, float* stats, int64_t stats_ld, int stats_rows,
-                const BnBwd& bb, const LazyArgs* lza, hipStream_t stream) {
-  // cfg = tile + 10 * panel (1: resident, 2: streamed) + 100 * stages (0: three, 1: two, 2: four; a
-  // four-stage request falls back to three where the counts or the LDS do not fit)
-  // + 1000 * family (fp32 only; 1: 32x64 wave tiles -- twice the waves of the 64x64 tiles for the
-  // small-M layers of small batches, where the 64x64 grid leaves SIMDs idle)
-  const int bres = (cfg / 10) % 10 == 0 ? -1 : ((cfg / 10) % 10 == 1 ? 1 : 0);
-  const int ns = (cfg / 100) % 10 == 1 ? 2 : ((cfg / 100) % 10 == 2 ? 4 : 3);
-  const int fam = (cfg / 1000) % 10;
-  cfg %= 10;
+int nt_dispatch(GK_NT_UNIT_ARGS) {
   auto a = static_cast<const T*>(A);
   auto b = static_cast<const T*>(B);
   auto c = static_cast<T*>(C);
-  const int cfg_req = cfg;   // the 32x64 family checks its own tile widths
-  if (cfg <= 0) cfg = N % 256 == 0 ? 3 : (N % 128 == 0 ? 2 : 1);
-  // tiles (BM x BN, waves): 1 256x64 (4)  2 256x128 (8)  3 128x256 (8)  4 128x128 (4)
-  //                         5 256x256 (8, 128x64 per wave)  6 256x128 (4, 128x64)  7 128x256 (4, 128x64)
-  // fp32 runs 64x64 wave tiles only (5-7 map to the 64x64 tile of the same block width)
-  static const int cfg_bn[8] = {64, 64, 128, 256, 128, 256, 128, 256};
-  if (cfg > 7 || N % cfg_bn[cfg] != 0) cfg = 1;   // the tile must divide N (B rows are not clamped)
+  const cfg::NtSel s = cfg::nt_select(w, N, sizeof(T) == 4, X6, bb.h != nullptr, lza != nullptr);
   const LazyA lz = lza ? LazyA{lza->x, lza->coef, lza->padz, lza->padx, lza->C} : LazyA{};
-#define GK_NTA(WM_, WN_, MSB_, BNB_, LZ_) \
-  return launch_nt_any<WM_, WN_, GATHER, MSB_, BNB_, T, LZ_, X6>(a, lda, b, ldb, c, ldc, M, N, K, max_blocks, bres, ns, geo, stats, stats_ld, stats_rows, bb, lz, stream)
+#define GK_NTA(WM_, WN_, MSB_, BNB_, LZ_)                                                                           \
+  case cfg::nt_key(WM_, WN_, MSB_, BNB_, LZ_):                                                                      \
+    return launch_nt_any<WM_, WN_, GATHER, MSB_, BNB_, T, LZ_, X6>(a, lda, b, ldb, c, ldc, M, N, K, max_blocks, s.panel, \
+                                                                   s.stages, geo, stats, stats_ld, stats_rows, bb, lz, stream)
+  // the four 64x64-wave-tile blocks and the seven 32x64 ones (case order = instantiation order)
+#define GK_NT64(BNB_, LZ_)          \
+  GK_NTA(4, 2, 4, BNB_, LZ_);       \
+  GK_NTA(2, 4, 4, BNB_, LZ_);       \
+  GK_NTA(2, 2, 4, BNB_, LZ_);       \
+  GK_NTA(4, 1, 4, BNB_, LZ_)
+#define GK_NT32(BNB_)               \
+  GK_NTA(2, 2, 2, BNB_, false);     \
+  GK_NTA(2, 1, 2, BNB_, false);     \
+  GK_NTA(1, 4, 2, BNB_, false);     \
+  GK_NTA(4, 2, 2, BNB_, false);     \
+  GK_NTA(2, 4, 2, BNB_, false);     \
+  GK_NTA(1, 2, 2, BNB_, false);     \
+  GK_NTA(4, 1, 2, BNB_, false)
+  const int key = cfg::nt_key(s.wm, s.wn, s.msb, s.bnb, s.lz);
   if constexpr (sizeof(T) == 4) {
-    if (lza) {   // lazy BN-backward A operand (fp32)
-      if (bb.h) {
-        switch (cfg) {
-          case 2: GK_NTA(4, 2, 4, true, true);
-          case 3: case 5: case 7: GK_NTA(2, 4, 4, true, true);
-          case 4: case 6: GK_NTA(2, 2, 4, true, true);
-          default: GK_NTA(4, 1, 4, true, true);
-        }
-      }
-      switch (cfg) {
-        case 2: GK_NTA(4, 2, 4, false, true);
-        case 3: case 5: case 7: GK_NTA(2, 4, 4, false, true);
-        case 4: case 6: GK_NTA(2, 2, 4, false, true);
-        default: GK_NTA(4, 1, 4, false, true);
+    switch (key) {
+      GK_NT64(true, true);   // lazy BN-backward A operand
+      GK_NT64(false, true);
+      GK_NT32(true);
+      GK_NT32(false);
+      GK_NT64(true, false);
+    }
+    if constexpr (X6) {   // bf16x6: 128x64 wave tiles
+      switch (key) {
+        GK_NTA(2, 4, 8, false, false);
+        GK_NTA(2, 2, 8, false, false);
+        GK_NTA(1, 4, 8, false, false);
       }
     }
-  }
-  if constexpr (sizeof(T) == 4) {
-    if (fam == 1 && !lza) {
-      // 32x64 wave tiles: 1 128x64 (4 waves)  2 64x128 (4)  3 64x64 (2)  4 32x256 (4)  5 128x128 (8)
-      //                   6 64x256 (8)  7 32x128 (2)
-      static const int bn32[8] = {64, 64, 128, 64, 256, 128, 256, 128};
-      cfg = cfg_req;
-      if (cfg <= 0 || cfg > 7 || N % bn32[cfg] != 0) cfg = 1;
-      if (bb.h) {
-        switch (cfg) {
-          case 2: GK_NTA(2, 2, 2, true, false);
-          case 3: GK_NTA(2, 1, 2, true, false);
-          case 4: GK_NTA(1, 4, 2, true, false);
-          case 5: GK_NTA(4, 2, 2, true, false);
-          case 6: GK_NTA(2, 4, 2, true, false);
-          case 7: GK_NTA(1, 2, 2, true, false);
-          default: GK_NTA(4, 1, 2, true, false);
-        }
-      }
-      switch (cfg) {
-        case 2: GK_NTA(2, 2, 2, false, false);
-        case 3: GK_NTA(2, 1, 2, false, false);
-        case 4: GK_NTA(1, 4, 2, false, false);
-        case 5: GK_NTA(4, 2, 2, false, false);
-        case 6: GK_NTA(2, 4, 2, false, false);
-        case 7: GK_NTA(1, 2, 2, false, false);
-        default: GK_NTA(4, 1, 2, false, false);
-      }
-    }
-  }
-  if (bb.h) {   // BN-backward epilogue: 64x64 wave tiles only
-    switch (cfg) {
-      case 2: GK_NTA(4, 2, 4, true, false);
-      case 3: case 5: case 7: GK_NTA(2, 4, 4, true, false);
-      case 4: case 6: GK_NTA(2, 2, 4, true, false);
-      default: GK_NTA(4, 1, 4, true, false);
-    }
-  }
-  if constexpr (sizeof(T) == 4) {
-    if constexpr (X6) {   // bf16x6: 128x64 wave tiles (fewer operand splits and LDS reads per product)
-      switch (cfg) {
-        case 5: GK_NTA(2, 4, 8, false, false);
-        case 6: GK_NTA(2, 2, 8, false, false);
-        case 7: GK_NTA(1, 4, 8, false, false);
-        default: break;
-      }
-    }
-    switch (cfg) {
-      case 2: GK_NTA(4, 2, 4, false, false);
-      case 3: case 5: GK_NTA(2, 4, 4, false, false);
-      case 7: GK_NTA(1, 4, 4, false, false);
-      case 4: case 6: GK_NTA(2, 2, 4, false, false);
-      default: GK_NTA(4, 1, 4, false, false);
+    switch (key) {
+      GK_NTA(4, 2, 4, false, false);
+      GK_NTA(2, 4, 4, false, false);
+      GK_NTA(1, 4, 4, false, false);
+      GK_NTA(2, 2, 4, false, false);
+      GK_NTA(4, 1, 4, false, false);
     }
   } else {
-    switch (cfg) {
-      case 2: GK_NTA(4, 2, 4, false, false);
-      case 3: GK_NTA(2, 4, 4, false, false);
-      case 4: GK_NTA(2, 2, 4, false, false);
-      case 5: GK_NTA(2, 4, 8, false, false);
-      case 6: GK_NTA(2, 2, 8, false, false);
-      case 7: GK_NTA(1, 4, 8, false, false);
-      default: GK_NTA(4, 1, 4, false, false);
+    switch (key) {
+      GK_NT64(true, false);
+      GK_NTA(4, 2, 4, false, false);
+      GK_NTA(2, 4, 4, false, false);
+      GK_NTA(2, 2, 4, false, false);
+      GK_NTA(2, 4, 8, false, false);
+      GK_NTA(2, 2, 8, false, false);
+      GK_NTA(1, 4, 8, false, false);
+      GK_NTA(4, 1, 4, false, false);
     }
   }
+#undef GK_NT32
+#undef GK_NT64
 #undef GK_NTA
+  return cfg::kDoesNotFit;   // not reached: nt_select names instantiated tiles only
 }
 
 template <int WN, int WK, int WS, bool GATHER, int MSN = 1>
@@ -2521,41 +2468,34 @@ void launch_tn_any(const uint16_t* G, int64_t ldg, const uint16_t* X, int64_t ld
   else launch_tn<WN, WK, WS, 2, GATHER, MSN>(G, ldg, X, ldx, W, ldw, M, N, K, splits, geo, stream);
 }
 
+// Reaches the instantiations that cfg::tn_select can name (gemm_cfg.h: tiles, fallbacks).
+// 128x64 per wave (MSN 2, one wave per SIMD to fit 340-460 VGPRs) measured 1.3-3x slower than
+// the 64x64 tiles on every BERT / ResNet-50 grad-weight shape (profiles/r02_tn_probe.json), so
+// no tile instantiates it; the template parameter stays for future occupancy experiments.
 template <bool GATHER>
 void tn_dispatch(const void* G, int64_t ldg, const void* X, int64_t ldx, float* W, int64_t ldw, int64_t M, int N,
-                 int K, int cfg, int splits, const ConvGeo& geo, hipStream_t stream) {
-  // cfg = tile digit + 10 * (1: two stages, 2: three) + 100 * tile group.
-  // tile = cfg % 10 + 10 * (cfg / 100), (WN, WK, WS), 64x64 per wave:
-  // 1 (1,1,4)  2 (2,1,2)  3 (1,2,2)  4 (2,2,1)  5 (4,1,1)  6 (1,4,1)  7 (2,2,2)  8 (1,1,2)
-  // 9 (4,2,1) 256x128  11 (2,4,1) 128x256  12 (4,4,1) 256x256 (16 waves): the large output
-  // tiles halve the LDS-DMA / L2 traffic per MFMA of the compute-bound (long-K) grad-weights
-  // 128x64 per wave (MSN 2, one wave per SIMD to fit 340-460 VGPRs) measured 1.3-3x slower than
-  // the 64x64 tiles on every BERT / ResNet-50 grad-weight shape (profiles/r02_tn_probe.json), so
-  // no tile instantiates it; the template parameter stays for future occupancy experiments.
-  const int ns = (cfg / 10) % 10 == 2 ? 3 : 2;
-  cfg = cfg % 10 + 10 * ((cfg / 100) % 10);
+                 int K, const cfg::TnWord& w, int splits, const ConvGeo& geo, hipStream_t stream) {
   auto g = static_cast<const uint16_t*>(G);
   auto x = static_cast<const uint16_t*>(X);
-  if (cfg <= 0) {
-    const bool n2 = N % 128 == 0, k2 = K % 128 == 0;
-    cfg = n2 && k2 ? 7 : (n2 ? 2 : (k2 ? 3 : 1));
+  const cfg::TnSel s = cfg::tn_select(w, N, K);
+#define GK_TN(WN_, WK_, WS_)           \
+  case cfg::tn_key(WN_, WK_, WS_):     \
+    launch_tn_any<WN_, WK_, WS_, GATHER>(g, ldg, x, ldx, W, ldw, M, N, K, splits, s.stages, geo, stream); \
+    break
+  switch (cfg::tn_key(s.wn, s.wk, s.ws)) {
+    GK_TN(4, 2, 1);
+    GK_TN(2, 4, 1);
+    GK_TN(4, 4, 1);
+    GK_TN(2, 1, 2);
+    GK_TN(1, 2, 2);
+    GK_TN(2, 2, 1);
+    GK_TN(4, 1, 1);
+    GK_TN(1, 4, 1);
+    GK_TN(2, 2, 2);
+    GK_TN(1, 1, 2);
+    GK_TN(1, 1, 4);
   }
-  static const int cfg_bn[13] = {64, 64, 128, 64, 128, 256, 64, 128, 64, 256, 64, 128, 256};
-  static const int cfg_bk[13] = {64, 64, 64, 128, 128, 64, 256, 128, 64, 128, 64, 256, 256};
-  if (cfg > 12 || cfg == 10 || N % cfg_bn[cfg] != 0 || K % cfg_bk[cfg] != 0) cfg = 1;   // tiles must divide N and K
-  switch (cfg) {
-    case 9: launch_tn_any<4, 2, 1, GATHER>(g, ldg, x, ldx, W, ldw, M, N, K, splits, ns, geo, stream); break;
-    case 11: launch_tn_any<2, 4, 1, GATHER>(g, ldg, x, ldx, W, ldw, M, N, K, splits, ns, geo, stream); break;
-    case 12: launch_tn_any<4, 4, 1, GATHER>(g, ldg, x, ldx, W, ldw, M, N, K, splits, ns, geo, stream); break;
-    case 2: launch_tn_any<2, 1, 2, GATHER>(g, ldg, x, ldx, W, ldw, M, N, K, splits, ns, geo, stream); break;
-    case 3: launch_tn_any<1, 2, 2, GATHER>(g, ldg, x, ldx, W, ldw, M, N, K, splits, ns, geo, stream); break;
-    case 4: launch_tn_any<2, 2, 1, GATHER>(g, ldg, x, ldx, W, ldw, M, N, K, splits, ns, geo, stream); break;
-    case 5: launch_tn_any<4, 1, 1, GATHER>(g, ldg, x, ldx, W, ldw, M, N, K, splits, ns, geo, stream); break;
-    case 6: launch_tn_any<1, 4, 1, GATHER>(g, ldg, x, ldx, W, ldw, M, N, K, splits, ns, geo, stream); break;
-    case 7: launch_tn_any<2, 2, 2, GATHER>(g, ldg, x, ldx, W, ldw, M, N, K, splits, ns, geo, stream); break;
-    case 8: launch_tn_any<1, 1, 2, GATHER>(g, ldg, x, ldx, W, ldw, M, N, K, splits, ns, geo, stream); break;
-    default: launch_tn_any<1, 1, 4, GATHER>(g, ldg, x, ldx, W, ldw, M, N, K, splits, ns, geo, stream); break;
-  }
+#undef GK_TN
 }
 
 

@@ -1,7 +1,7 @@
 """fp32 matmul algorithm selection (ops/conv1x1.py set_f32_matmul) on the CPU:
 the bf16x6 candidates are offered only in "bf16x6" mode and only for fp32
-operands, their cfgs carry the 100000 digit (gemm.hip nt_unit_f32 /
-tn_unit_f32x), split-K keeps both digits, autotune keys are tagged so the two
+operands, their cfgs carry the 100000 digit (gemm_cfg.h product
+family), split-K keeps both digits, autotune keys are tagged so the two
 modes never share a cached choice, and bench.py defaults to bf16x6.
 
 The split itself (exact hi + mid + lo decomposition, six products of order
