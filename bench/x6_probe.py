@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """fp32 GEMMs on the fp32 MFMA (v_mfma_f32_16x16x4_f32) vs the bf16x6
-fp32-accurate products (gemm_kern.h X6: exact 3-way bf16 split, six part
+fp32-accurate products (gemm_nt.h X6: exact 3-way bf16 split, six part
 products on v_mfma_f32_16x16x32_bf16): best time over a set of tile configs
 and the error of each against an fp64 reference, on the ResNet-50 bs512 1x1 /
 implicit-GEMM shapes and the BERT-base linear shapes.

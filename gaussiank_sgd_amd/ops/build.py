@@ -5,8 +5,8 @@ No hipify, no JIT cache: HIP kernels are compiled with ``hipcc
 the torch headers, then linked into one shared object next to the package so
 it travels to the GPU box with the source tree.
 
-Objects are cached under ``build/`` keyed by a hash of (source, headers,
-flags); ``python -m gaussiank_sgd_amd.ops.build`` rebuilds what changed.
+Objects are cached under ``build/`` keyed by a hash of (source, the headers it
+includes, flags); ``python -m gaussiank_sgd_amd.ops.build`` rebuilds what changed.
 """
 from __future__ import annotations
 
@@ -14,6 +14,7 @@ import argparse
 import concurrent.futures as cf
 import hashlib
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -45,6 +46,8 @@ if VARIANT and not ASAN:
 ARCH = os.environ.get("GKSGD_OFFLOAD_ARCH", "gfx950")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
+# the kernel family (gemm_<family>.h) that GEMM instantiation unit 0, 1, ... is made from
+GEMM_UNIT_FAMILY = ["nt", "nt", "nt", "nt", "tn", "nt", "nt", "tn", "nt_x62", "tn_x62", "nt_x62"]
 HIP_SOURCES = [
     "kernels/compress.hip",
     "kernels/quality.hip",
@@ -52,8 +55,8 @@ HIP_SOURCES = [
     "kernels/optim.hip",
     "kernels/bn_act.hip",
     "kernels/gemm.hip",
-    # gemm_inst.hip: one object per GEMM instantiation unit (-DGK_GEMM_UNIT=<n>, gemm_kern.h)
-    *["kernels/gemm_inst.hip#%d" % u for u in range(11)],
+    # gemm_inst_<family>.hip: one object per GEMM instantiation unit (-DGK_GEMM_UNIT=<n>, gemm_units.h)
+    *["kernels/gemm_inst_%s.hip#%d" % (f, u) for u, f in enumerate(GEMM_UNIT_FAMILY)],
     "kernels/ln.hip",
     "kernels/linear.hip",
     "kernels/lstm.hip",
@@ -72,16 +75,13 @@ CXX_SOURCES = [
     "comm/rccl_engine.cpp",
     "bindings.cpp",
 ]
-HEADERS = ["kernels/common.h", "kernels/gk_kernels.h", "kernels/mfma_util.h", "kernels/gemm_kern.h",
-           "kernels/gemm_cfg.h",
-           "kernels/wino_x6_common.h",
-           "comm/rccl_engine.h"]
 # per-file extra flags: the sparse aggregation must round product and sum
 # separately (bit-identical to the reference arithmetic and the CPU mirror)
 # the GEMM units: no SLP vectorisation -- packed fp32 VALU (v_pk_add_f32) beside
 # MFMAs costs more issue cycles than scalar pairs (MI355X_MICROARCH.md constants);
 # measured on the bf16x6 split: GEMMs 2.5-4.5% faster (r5c20)
-EXTRA_FLAGS = {"kernels/scatter.hip": ["-ffp-contract=off"], "kernels/gemm_inst.hip": ["-fno-slp-vectorize"]}
+EXTRA_FLAGS = {"kernels/scatter.hip": ["-ffp-contract=off"],
+               **{"kernels/gemm_inst_%s.hip" % f: ["-fno-slp-vectorize"] for f in set(GEMM_UNIT_FAMILY)}}
 
 
 def _torch_dirs():
@@ -135,13 +135,25 @@ def _cxx_flags() -> List[str]:
     ]
 
 
+def _closure(src: Path) -> List[Path]:
+    """``src`` and every file its quoted ``#include`` lines reach, resolved as the compiler does
+    with the -I flags above: the including file's directory, then csrc/, then csrc/kernels/.
+    Preprocessor conditionals are not evaluated (the closure can only be too large)."""
+    seen: List[Path] = [src]
+    for f in seen:   # grows while it is walked
+        for name in re.findall(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', f.read_text(), re.M):
+            hits = [d / name for d in (f.parent, CSRC, CSRC / "kernels") if (d / name).is_file()]
+            if not hits:
+                raise FileNotFoundError('%s: #include "%s" resolves to no file' % (f, name))
+            if Path(os.path.normpath(hits[0])) not in seen:
+                seen.append(Path(os.path.normpath(hits[0])))
+    return seen
+
+
 def _digest(src: Path, flags: List[str]) -> str:
     h = hashlib.sha256()
-    h.update(src.read_bytes())
-    for hd in HEADERS:
-        p = CSRC / hd
-        if p.exists():
-            h.update(p.read_bytes())
+    for p in sorted(_closure(src)):
+        h.update(p.read_bytes())
     h.update(" ".join(flags).encode())
     return h.hexdigest()[:16]
 

@@ -80,7 +80,7 @@ _TN_SMALL_F32 = [(c, s) for c in (4, 5, 11, 14, 15) for s in (16, 32, 128)]
 # fp32 matmul algorithm (GKSGD_F32_MATMUL / set_f32_matmul):
 #   "native" -- fp32 operands on v_mfma_f32_16x16x4_f32 only;
 #   "bf16x6" -- the fp32 GEMM / implicit-GEMM candidates also include the bf16x6
-#   kernels (gemm_kern.h X6, cfg digit 100000): every fp32 operand split exactly
+#   kernels (gemm_nt.h / gemm_tn_f32.h X6, cfg digit 100000): every fp32 operand split exactly
 #   into three bf16 parts, the six part products of order <= 2 accumulated in
 #   fp32 on v_mfma_f32_16x16x32_bf16 -- measured MORE accurate than the fp32
 #   MFMA against an fp64 reference on every ResNet-50 / BERT shape
@@ -88,7 +88,7 @@ _TN_SMALL_F32 = [(c, s) for c in (4, 5, 11, 14, 15) for s in (16, 32, 128)]
 #   not a reduced precision; the tuner picks the faster kernel per shape.
 X6 = 100000
 _NT_CFGS_X6 = [c + X6 for c in (1, 2, 3, 4, 5, 6, 7, 12, 13, 101, 102, 103, 104, 105, 106, 107, 202, 203, 1001, 1002, 1003)]
-# register-staged bf16x6 row GEMMs (gemm_kern.h gemm_nt_x62_kernel, cfg digit 200000; tiles 1-7):
+# register-staged bf16x6 row GEMMs (gemm_nt_x62.h gemm_nt_x62_kernel, cfg digit 200000; tiles 1-7):
 # plain row GEMMs only -- an implicit-GEMM / lazy / split-K call refuses them and the tuner moves on.
 # Digit 300000: the same kernels with B split into bf16 planes once per call by the binding
 # (split3_rows), no B split in the kernel: within +-3% of 200000, up to 8% faster on a few shapes (r5c33)
@@ -116,7 +116,7 @@ def _x6() -> bool:
     return _F32MM == "bf16x6"
 
 
-# register-staged bf16x6 grad-weight (gemm_kern.h gemm_tn_x62_kernel, cfg digit 200000; tiles 1-8):
+# register-staged bf16x6 grad-weight (gemm_tn_x62.h gemm_tn_x62_kernel, cfg digit 200000; tiles 1-8):
 # plain row form only -- an implicit-GEMM / lazy call refuses them and the tuner moves on
 _TN_CFGS_X62 = [(2 * X6 + t, sp) for t in (1, 2, 3, 4, 5, 6, 7, 8) for sp in (0, 64)]
 
@@ -664,7 +664,7 @@ def _wgrad_into(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, s: int, out_
         return
     sp = ch[2]
     if side and sp == 0 and _SIDE_QROUNDS > 0:
-        sp = -_SIDE_QROUNDS     # a smaller auto grid beside the critical path (gemm_kern.h launch_tn*)
+        sp = -_SIDE_QROUNDS     # a smaller auto grid beside the critical path (gemm_tn*.h launch_tn*)
     run(out_f32, ch[1], sp)
 
 

@@ -26,8 +26,15 @@
 //   transpose read: 4 rows x 16 columns of 16-bit data delivered column-wise).
 //   Each block reduces a contiguous slice of M for one output tile and adds
 //   its fp32 partial into the (gradient-arena) output with float atomics.
+//
+// The kernel templates are in one header per family -- gemm_nt.h, gemm_tn.h,
+// gemm_tn_f32.h, gemm_nt_x62.h, gemm_tn_x62.h -- instantiated by the units of
+// gemm_inst_*.hip (compiled in parallel, ops/build.py); this file holds the
+// public entry points and sees only the units' declarations (gemm_units.h).
+#include "common.h"
 #include "gemm_cfg.h"
-#include "gemm_kern.h"
+#include "gemm_units.h"
+#include "mfma_util.h"
 
 namespace gk {
 

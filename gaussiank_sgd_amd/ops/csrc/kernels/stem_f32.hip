@@ -265,7 +265,7 @@ stem_f32_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ dy,
 }
 
 // ---------------------------------------------------------------------------
-// bf16x6 forward (fp32-accurate on the bf16 matrix cores, as gemm_kern.h X6):
+// bf16x6 forward (fp32-accurate on the bf16 matrix cores, as gemm_nt.h X6):
 // the weights are split ONCE per call into three exact bf16 planes [3][64][160]
 // (stem_w_split3_kernel; taps >= 147 zero), the band's activations are split
 // in registers (mfma_util.h split3x8), and the six part products of order

@@ -12,7 +12,7 @@ namespace {
 
 // 16-byte chunk q of a U row r (32 bf16 input channels) lives at chunk
 // q ^ wx6_swz(r): a fragment read of 16 rows x one chunk spreads over all
-// bank slots (the x62 GEMM image, gemm_kern.h x62_swz)
+// bank slots (the x62 GEMM image, gemm_common.h x62_swz)
 __host__ __device__ __forceinline__ int wx6_swz(int r) { return ((r >> 3) & 1) << 1; }
 
 __device__ __forceinline__ uint16_t wx6_bf16(float f) { return (uint16_t)(pack_bf16x2(f, 0.f) & 0xffffu); }

@@ -105,7 +105,7 @@ def test_bench_defaults_to_bf16x6(monkeypatch):
 
 
 def _xcd_remap2(L_x, L_y, gx, gy):
-    """Python mirror of gemm_kern.h xcd_remap2 (GK_XCD_REMAP = 1)."""
+    """Python mirror of gemm_common.h xcd_remap2 (GK_XCD_REMAP = 1)."""
     G = gx * gy
     if G % 8 or G < 16:
         return L_x, L_y

@@ -1,4 +1,4 @@
-"""bf16x6 fp32 GEMMs (ops/csrc/kernels/gemm_kern.h X6, cfg digit 100000):
+"""bf16x6 fp32 GEMMs (ops/csrc/kernels/gemm_nt.h / gemm_tn_f32.h X6, cfg digit 100000):
 fp32 operands split exactly into three bf16 parts, the six part products of
 order <= 2 accumulated in fp32 on v_mfma_f32_16x16x32_bf16.  Checked against
 an fp64 PyTorch reference at the SAME tolerances as the fp32-MFMA kernels
