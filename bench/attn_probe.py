@@ -2,7 +2,13 @@
 (B 32, heads 12, T 512, d 64, dropout 0.1): forward and forward+backward
 times per call and the achieved MFMA rate (fwd 4*B*H*T^2*d FLOPs, bwd 2.5x).
 
-    python bench/attn_probe.py [--B 32] [--T 512] [--heads 12] [--p 0.1]
+    python bench/attn_probe.py [--B 32] [--T 512] [--heads 12] [--p 0.1] [--dtype bf16|fp32] [--pad]
+
+--pad: a key-padding mask with per-sequence valid lengths drawn uniformly from
+[T/4, T] (fixed seed).  Times ours with the mask ("ours_masked") against SDPA
+with the same boolean mask ("sdpa_masked"), and ours with an all-valid mask
+("ours_allvalid") against ours without one ("ours"); the TFLOP/s of the masked
+rows count the dense op's FLOPs.
 """
 import argparse
 import json
@@ -35,33 +41,49 @@ def main():
     ap.add_argument("--T", type=int, default=512)
     ap.add_argument("--heads", type=int, default=12)
     ap.add_argument("--p", type=float, default=0.1)
+    ap.add_argument("--dtype", choices=["bf16", "fp32"], default="bf16")
+    ap.add_argument("--pad", action="store_true", help="key-padding mask, valid lengths uniform in [T/4, T]")
+    ap.add_argument("--only", default="", help="comma-separated rows to time (default: all)")
     ap.add_argument("--json-out", default="")
     a = ap.parse_args()
     assert ops.load(), ops._load_error
     B, T, Hh, p = a.B, a.T, a.heads, a.p
+    dtype = torch.bfloat16 if a.dtype == "bf16" else torch.float32
+    fn = attention._FlashAttnFn if a.dtype == "bf16" else attention._FlashAttnF32Fn
     torch.manual_seed(0)
-    qkv = torch.randn(B, T, 3 * Hh * 64, device="cuda").to(torch.bfloat16).requires_grad_(True)
-    dout = torch.randn(B, T, Hh * 64, device="cuda").to(torch.bfloat16)
+    qkv = torch.randn(B, T, 3 * Hh * 64, device="cuda").to(dtype).requires_grad_(True)
+    dout = torch.randn(B, T, Hh * 64, device="cuda").to(dtype)
     flops = 4.0 * B * Hh * T * T * 64
-    res = {"shape": [B, Hh, T, 64], "p": p}
+    res = {"shape": [B, Hh, T, 64], "p": p, "dtype": a.dtype}
 
-    def ours_f():
-        with torch.no_grad():
-            attention._FlashAttnFn.apply(qkv, Hh, p, 1)
+    def pair(call):
+        def f():
+            with torch.no_grad():
+                call()
 
-    def ours_fb():
-        o = attention._FlashAttnFn.apply(qkv, Hh, p, 1)
-        o.backward(dout)
+        def fb():
+            call().backward(dout)
+        return f, fb
 
-    def sdpa_f():
-        with torch.no_grad():
-            attention._sdpa(qkv, Hh, p)
+    rows = [("ours", *pair(lambda: fn.apply(qkv, Hh, p, 1))),
+            ("sdpa", *pair(lambda: attention._sdpa(qkv, Hh, p)))]
+    if a.pad:
+        g = torch.Generator().manual_seed(1234)
+        lengths = torch.randint(T // 4, T + 1, (B,), generator=g).cuda()
+        valid = torch.arange(T, device="cuda")[None, :] < lengths[:, None]
+        bits = attention.pack_key_mask(valid)
+        ones = attention.pack_key_mask(torch.ones_like(valid))
+        bmask = valid[:, None, None, :]
+        res["pad"] = {"mean_valid": round(float(valid.float().mean()), 4), "min_len": int(lengths.min()),
+                      "max_len": int(lengths.max())}
+        rows += [("ours_masked", *pair(lambda: fn.apply(qkv, Hh, p, 1, None, bits))),
+                 ("ours_allvalid", *pair(lambda: fn.apply(qkv, Hh, p, 1, None, ones))),
+                 ("sdpa_masked", *pair(lambda: attention._sdpa(qkv, Hh, p, bmask)))]
 
-    def sdpa_fb():
-        o = attention._sdpa(qkv, Hh, p)
-        o.backward(dout)
-
-    for name, f, fb in [("ours", ours_f, ours_fb), ("sdpa", sdpa_f, sdpa_fb)]:
+    only = set(filter(None, a.only.split(",")))
+    for name, f, fb in rows:
+        if only and name not in only:
+            continue
         tf = timeit(f)
         tfb = timeit(fb)
         res[name] = {"fwd_us": round(tf, 1), "fwd_bwd_us": round(tfb, 1), "bwd_us": round(tfb - tf, 1),

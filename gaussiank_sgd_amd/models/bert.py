@@ -3,8 +3,10 @@
 Standard BERT-base: vocab 30522, hidden 768, 12 layers, 12 heads, FFN 3072,
 512 positions, GELU, post-LN, MLM head tied to the word embeddings
 (~110M parameters).  On the GPU, attention is the flash-style HIP kernel of
-ops/attention.py on the packed QKV projection (no head split / merge copies);
-with an attention mask or on the CPU it is ``F.scaled_dot_product_attention``.
+ops/attention.py on the packed QKV projection (no head split / merge copies),
+with ``attention_mask`` (key padding) packed to bits once per forward and
+honoured inside the kernels; on the CPU, or for shapes the kernels do not
+take, it is ``F.scaled_dot_product_attention``.
 Run under bf16 autocast.  Every encoder / MLM-head
 linear is a ``FastLinear`` (ops/linear.py: autotuned MFMA GEMMs, GELU backward
 and bias gradient in one fused pass into the fp32 gradient arena).  Gradients stay fp32 in
@@ -79,13 +81,17 @@ class BertLayer(nn.Module):
         self.drop = nn.Dropout(c.dropout)
         self.p = c.dropout
 
-    def forward(self, x, attn_mask=None):
+    def forward(self, x, attn_mask=None, key_mask=None):
+        """``key_mask``: a key-padding mask, [B, T] (nonzero = real token) or the
+        packed bits of ``attention.pack_key_mask``; the fused kernels take it.
+        ``attn_mask`` (any SDPA mask) forces the SDPA path."""
         B, T, H = x.shape
         y = self.qkv(x)
         if attn_mask is None and attention.fused_available(y, self.heads):
             # flash-style HIP attention straight on the packed projection (ops/attention.py)
-            a = attention.self_attention(y, self.heads, self.p, self.training)
+            a = attention.self_attention(y, self.heads, self.p, self.training, key_mask=key_mask)
         else:
+            attn_mask = attention.merge_masks(attn_mask, key_mask, B, T)
             q, k, v = _SplitHeads.apply(y, self.heads)
             a = F.scaled_dot_product_attention(q, k, v, attn_mask=attn_mask,
                                                dropout_p=self.p if self.training else 0.0)
@@ -131,11 +137,16 @@ class BertForMaskedLM(nn.Module):
         x = bert_embeddings(input_ids, token_type_ids, self.word_embeddings, self.position_embeddings,
                             self.token_type_embeddings)
         x = self.emb_drop(self.emb_ln(x))
-        mask = None
+        mask = key_bits = None
         if attention_mask is not None:
-            mask = attention_mask[:, None, None, :].to(torch.bool)
+            B, T = attention_mask.shape
+            if attention.fused_available_for(x, T, self.config.heads, self.config.hidden):
+                # the fused kernels take the padding mask as bits: packed once, shared by every layer
+                key_bits = attention.pack_key_mask(attention_mask)
+            else:
+                mask = attention_mask[:, None, None, :].to(torch.bool)
         for layer in self.encoder:
-            x = layer(x, mask)
+            x = layer(x, mask, key_bits)
         if masked_positions is not None:
             x = x.gather(1, masked_positions.unsqueeze(-1).expand(-1, -1, x.shape[-1]))
         h = self.mlm_ln(self.mlm_dense(x, act="gelu"))

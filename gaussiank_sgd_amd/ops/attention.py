@@ -10,8 +10,21 @@ two backward (dQ with ``delta = rowsum(dO * O)``, then dK / dV); nothing of
 size T x T is stored and there are no head split / merge copies: the kernels
 read q, k, v with the packed row stride and write ``dqkv`` in the projection's
 own layout.  The dropout mask is a hash of (seed, b*heads + h, query, key),
-regenerated in the backward.  Elsewhere (CPU, masks, other head dims)
-it is ``F.scaled_dot_product_attention`` with identical semantics.
+regenerated in the backward.
+
+``key_mask`` is a key-padding mask: ``[B, T]`` (nonzero = real token) or the
+packed bits of ``pack_key_mask`` (int32 ``[B, T // 32]``, bit ``j`` of word
+``w`` = key ``32 w + j``).  The kernels take the bits: masked keys get
+probability 0 (``softmax(q k^T / 8 + (valid ? 0 : -inf))``) and zero dK / dV,
+key tiles without a valid key cost no arithmetic, and every query row --
+padded ones too -- is computed, as SDPA does with a key mask.  The masked
+bf16 forward also keeps the rounding residue of its output (``out_lo``) for the
+backward's ``delta``, which short sequences need (few keys, concentrated
+probabilities).  A sequence
+without any valid key gives zeros (output and gradients) where SDPA gives NaN.
+
+Elsewhere (CPU, ``attn_mask``, other head dims) it is
+``F.scaled_dot_product_attention`` with identical semantics.
 
 Not in the reference (its model zoo has no transformer); BASELINE config 5
 (BERT-base MLM) runs it.
@@ -57,13 +70,72 @@ def dropout_mask(B: int, heads: int, T: int, p: float, seed: int, device, seed_d
     return (u >= drop_threshold(p)).view(B, heads, T, T)
 
 
-def reference_attention(qkv: torch.Tensor, heads: int, p: float = 0.0, seed: int = 0) -> torch.Tensor:
-    """fp32 composition with the kernels' exact dropout mask (autograd-able)."""
+def pack_key_mask(mask: torch.Tensor) -> torch.Tensor:
+    """``[B, T]`` key mask (any dtype, nonzero = valid) -> packed bits, int32
+    ``[B, T // 32]``: bit ``j`` of word ``w`` is key ``32 w + j``.  One HIP launch
+    on the GPU, a torch expression on the CPU; nothing is read back to the host."""
+    if mask.dim() != 2 or mask.shape[1] % 32:
+        raise ValueError("key mask must be [B, T] with T a multiple of 32, got %s" % (tuple(mask.shape),))
+    B, T = mask.shape
+    if mask.is_cuda and load():
+        bits = torch.empty(B, T // 32, dtype=torch.int32, device=mask.device)
+        _ops().attn_pack_key_mask(mask.contiguous(), bits)
+        return bits
+    m = (mask != 0).view(B, T // 32, 32).to(torch.int64)
+    w = (m << torch.arange(32, device=mask.device)).sum(-1)
+    return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
+
+
+def unpack_key_mask(bits: torch.Tensor, T: int) -> torch.Tensor:
+    """Packed bits int32 ``[B, T // 32]`` -> bool ``[B, T]`` (True = valid)."""
+    B = bits.shape[0]
+    sh = torch.arange(32, device=bits.device)
+    return ((bits.reshape(B, T // 32, 1).to(torch.int64) >> sh) & 1).bool().view(B, T)
+
+
+def _is_packed(key_mask: torch.Tensor, B: int, T: int) -> bool:
+    """A packed int32 [B, T // 32] mask, as opposed to a [B, T] one (dtype and shape tell)."""
+    if key_mask.dtype == torch.int32 and tuple(key_mask.shape) == (B, T // 32) and T % 32 == 0:
+        return True
+    if tuple(key_mask.shape) != (B, T):
+        raise ValueError("key_mask must be [B, T] = [%d, %d] or packed int32 [B, T // 32], got %s %s"
+                         % (B, T, tuple(key_mask.shape), key_mask.dtype))
+    return False
+
+
+def _key_bits(key_mask: torch.Tensor, B: int, T: int) -> torch.Tensor:
+    return key_mask.contiguous() if _is_packed(key_mask, B, T) else pack_key_mask(key_mask)
+
+
+def key_mask_bool(key_mask: torch.Tensor, B: int, T: int) -> torch.Tensor:
+    """Either form of a key mask as bool ``[B, T]``."""
+    return unpack_key_mask(key_mask, T) if _is_packed(key_mask, B, T) else key_mask != 0
+
+
+def merge_masks(attn_mask, key_mask, B: int, T: int):
+    """The SDPA mask of ``attn_mask`` (bool or additive, or None) and a key mask
+    (either form, or None): masked keys are excluded for every query."""
+    if key_mask is None:
+        return attn_mask
+    km = key_mask_bool(key_mask, B, T)[:, None, None, :]
+    if attn_mask is None:
+        return km
+    if attn_mask.dtype == torch.bool:
+        return attn_mask & km
+    return attn_mask.masked_fill(~km, float("-inf"))
+
+
+def reference_attention(qkv: torch.Tensor, heads: int, p: float = 0.0, seed: int = 0,
+                        key_mask=None) -> torch.Tensor:
+    """fp32 composition with the kernels' exact dropout mask (autograd-able);
+    ``key_mask``: masked keys score -inf."""
     B, T, H3 = qkv.shape
     d = H3 // (3 * heads)
     x = qkv.float().view(B, T, 3, heads, d)
     q, k, v = (x[:, :, i].transpose(1, 2) for i in range(3))
     s = torch.matmul(q, k.transpose(-1, -2)) / d ** 0.5
+    if key_mask is not None:
+        s = s.masked_fill(~key_mask_bool(key_mask, B, T)[:, None, None, :], float("-inf"))
     a = torch.softmax(s, dim=-1)
     if p > 0:
         keep = dropout_mask(B, heads, T, p, seed, qkv.device)
@@ -74,25 +146,29 @@ def reference_attention(qkv: torch.Tensor, heads: int, p: float = 0.0, seed: int
 
 class _FlashAttnFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, heads, p, seed, seed_dev=None):
+    def forward(ctx, qkv, heads, p, seed, seed_dev=None, key_bits=None):
         # seed_dev: the graph replay word (ops.graph_seed_word) under capture --
         # forward and backward of one replay read the same word
+        # key_bits: the packed key mask (pack_key_mask), shared with the backward
         B, T, _ = qkv.shape
         out = torch.empty(B, T, heads * HEAD_DIM, dtype=torch.bfloat16, device=qkv.device)
         lse = torch.empty(B * heads * T, dtype=torch.float32, device=qkv.device)
-        _ops().attn_fwd(qkv, out, lse, int(heads), float(p), int(seed), seed_dev)
-        ctx.save_for_backward(qkv, out, lse)
+        # with a mask, rows with few valid keys have concentrated probabilities, where dP and delta =
+        # rowsum(dO * O) nearly cancel: the forward also keeps what the bf16 rounding of O dropped
+        out_lo = None if key_bits is None else torch.empty_like(out)
+        _ops().attn_fwd(qkv, out, lse, int(heads), float(p), int(seed), seed_dev, key_bits, out_lo)
+        ctx.save_for_backward(qkv, out, lse, key_bits, out_lo)
         ctx.heads, ctx.p, ctx.seed, ctx.seed_dev = int(heads), float(p), int(seed), seed_dev
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        qkv, out, lse = ctx.saved_tensors
+        qkv, out, lse, key_bits, out_lo = ctx.saved_tensors
         dout = dout.to(torch.bfloat16).contiguous()
         delta = torch.empty_like(lse)
         dqkv = torch.empty_like(qkv)
-        _ops().attn_bwd(qkv, out, dout, lse, delta, dqkv, ctx.heads, ctx.p, ctx.seed, ctx.seed_dev)
-        return dqkv, None, None, None, None
+        _ops().attn_bwd(qkv, out, dout, lse, delta, dqkv, ctx.heads, ctx.p, ctx.seed, ctx.seed_dev, key_bits, out_lo)
+        return dqkv, None, None, None, None, None
 
 
 class _FlashAttnF32Fn(torch.autograd.Function):
@@ -100,23 +176,23 @@ class _FlashAttnF32Fn(torch.autograd.Function):
     v_mfma_f32_16x16x4_f32, the same dropout hashes."""
 
     @staticmethod
-    def forward(ctx, qkv, heads, p, seed, seed_dev=None):
+    def forward(ctx, qkv, heads, p, seed, seed_dev=None, key_bits=None):
         B, T, _ = qkv.shape
         out = torch.empty(B, T, heads * HEAD_DIM, dtype=torch.float32, device=qkv.device)
         lse = torch.empty(B * heads * T, dtype=torch.float32, device=qkv.device)
-        _ops().attn_f32_fwd(qkv, out, lse, int(heads), float(p), int(seed), seed_dev)
-        ctx.save_for_backward(qkv, out, lse)
+        _ops().attn_f32_fwd(qkv, out, lse, int(heads), float(p), int(seed), seed_dev, key_bits)
+        ctx.save_for_backward(qkv, out, lse, key_bits)
         ctx.heads, ctx.p, ctx.seed, ctx.seed_dev = int(heads), float(p), int(seed), seed_dev
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        qkv, out, lse = ctx.saved_tensors
+        qkv, out, lse, key_bits = ctx.saved_tensors
         dout = dout.to(torch.float32).contiguous()
         delta = torch.empty_like(lse)
         dqkv = torch.empty_like(qkv)
-        _ops().attn_f32_bwd(qkv, out, dout, lse, delta, dqkv, ctx.heads, ctx.p, ctx.seed, ctx.seed_dev)
-        return dqkv, None, None, None, None
+        _ops().attn_f32_bwd(qkv, out, dout, lse, delta, dqkv, ctx.heads, ctx.p, ctx.seed, ctx.seed_dev, key_bits)
+        return dqkv, None, None, None, None, None
 
 
 def _compute_dtype(qkv: torch.Tensor):
@@ -128,17 +204,31 @@ def _compute_dtype(qkv: torch.Tensor):
     return qkv.dtype if qkv.dtype in (torch.bfloat16, torch.float32) else None
 
 
-def fused_available(qkv: torch.Tensor, heads: int) -> bool:
-    """The HIP kernels take this call: bf16 (autocast or bf16 activations) or
-    fp32 (no autocast: the reference's precision), head dim 64, T % 128 == 0."""
-    if not qkv.is_cuda or qkv.dim() != 3 or qkv.shape[-1] != 3 * heads * HEAD_DIM:
+def _kernels_take(t: torch.Tensor, T: int, heads: int, width: int) -> bool:
+    """The one rule behind ``fused_available`` and ``fused_available_for``: ``t``
+    gives the device and the compute dtype, ``width`` is heads * head dim."""
+    if not t.is_cuda or width != heads * HEAD_DIM:
         return False
-    dt = _compute_dtype(qkv)
+    dt = _compute_dtype(t)
     if dt is None or not load():
         return False
     if dt == torch.float32:
-        return bool(_ops().attn_f32_supported(qkv.shape[1], HEAD_DIM))
-    return bool(_ops().attn_supported(qkv.shape[1], HEAD_DIM))
+        return bool(_ops().attn_f32_supported(T, HEAD_DIM))
+    return bool(_ops().attn_supported(T, HEAD_DIM))
+
+
+def fused_available(qkv: torch.Tensor, heads: int) -> bool:
+    """The HIP kernels take this call: bf16 (autocast or bf16 activations) or
+    fp32 (no autocast: the reference's precision), head dim 64, T % 128 == 0."""
+    if qkv.dim() != 3:
+        return False
+    return _kernels_take(qkv, qkv.shape[1], heads, qkv.shape[-1] // 3 if qkv.shape[-1] % 3 == 0 else -1)
+
+
+def fused_available_for(x: torch.Tensor, T: int, heads: int, width: int) -> bool:
+    """``fused_available`` for the QKV projection of activations ``x`` ([B, T,
+    width]) before it is computed: same device, same compute dtype."""
+    return _kernels_take(x, T, heads, width)
 
 
 def _sdpa(qkv: torch.Tensor, heads: int, p: float, attn_mask=None) -> torch.Tensor:
@@ -151,14 +241,22 @@ def _sdpa(qkv: torch.Tensor, heads: int, p: float, attn_mask=None) -> torch.Tens
 
 
 def self_attention(qkv: torch.Tensor, heads: int, p: float = 0.0, training: bool = True,
-                   attn_mask=None, seed: int = None) -> torch.Tensor:
-    """``[B, T, 3*heads*d]`` packed projection -> ``[B, T, heads*d]`` attention output."""
+                   attn_mask=None, seed: int = None, key_mask=None) -> torch.Tensor:
+    """``[B, T, 3*heads*d]`` packed projection -> ``[B, T, heads*d]`` attention output.
+    ``key_mask``: a key-padding mask, ``[B, T]`` (nonzero = valid) or packed
+    (``pack_key_mask``); the fused kernels take it, ``attn_mask`` forces SDPA.
+    An all-valid mask gives the unmasked call's output bit for bit; its bf16
+    gradients agree with it only to rounding, because the masked backward forms
+    ``delta`` from the output plus its saved rounding residue (``out_lo``, one
+    more bf16 [B, T, heads*d] activation kept per call)."""
     p = float(p) if training else 0.0
+    B, T = qkv.shape[0], qkv.shape[1]
     if attn_mask is None and fused_available(qkv, heads):
         if seed is None:
             seed = int(torch.randint(0, 2 ** 31 - 1, (1,), generator=seed_generator())) if p > 0 else 0
         seed_dev = capture_seed_word(qkv.device) if p > 0 else None
+        bits = None if key_mask is None else _key_bits(key_mask, B, T)   # packed once, kept for the backward
         if _compute_dtype(qkv) == torch.float32:
-            return _FlashAttnF32Fn.apply(qkv.contiguous(), heads, p, seed, seed_dev)
-        return _FlashAttnFn.apply(qkv.to(torch.bfloat16).contiguous(), heads, p, seed, seed_dev)
-    return _sdpa(qkv, heads, p, attn_mask)
+            return _FlashAttnF32Fn.apply(qkv.contiguous(), heads, p, seed, seed_dev, bits)
+        return _FlashAttnFn.apply(qkv.to(torch.bfloat16).contiguous(), heads, p, seed, seed_dev, bits)
+    return _sdpa(qkv, heads, p, merge_masks(attn_mask, key_mask, B, T))

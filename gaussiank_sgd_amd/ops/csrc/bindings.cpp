@@ -1788,8 +1788,26 @@ void check_attn_f32(const at::Tensor& t, const char* name, int64_t n) {
               name, " must be a contiguous fp32 GPU tensor of ", n, " elements");
 }
 
+// packed key mask: int32 [B, T / 32] on qkv's device (kernels/attn_mask.h); null when absent
+const uint32_t* key_bits_ptr(const c10::optional<at::Tensor>& t, const at::Tensor& qkv, int64_t B, int64_t T) {
+  if (!t.has_value() || !t->defined()) return nullptr;
+  TORCH_CHECK(t->is_cuda() && t->device() == qkv.device() && t->scalar_type() == at::kInt && t->is_contiguous() &&
+                  t->numel() == B * T / 32,
+              "key_bits must be a contiguous int32 tensor of B * T / 32 = ", B * T / 32, " words on qkv's device");
+  return reinterpret_cast<const uint32_t*>(t->data_ptr<int32_t>());
+}
+
+// the output's rounding residue (bf16, with key_bits only); null when absent
+void* out_lo_ptr(const c10::optional<at::Tensor>& t, const uint32_t* key_bits, int64_t rows, int64_t cols) {
+  if (!t.has_value() || !t->defined()) return nullptr;
+  TORCH_CHECK(key_bits != nullptr, "out_lo needs key_bits (only the masked kernels take it)");
+  check_attn(*t, "out_lo", rows, cols);
+  return t->data_ptr();
+}
+
 void attn_fwd(at::Tensor qkv, at::Tensor out, at::Tensor lse, int64_t heads, double p, int64_t seed,
-              c10::optional<at::Tensor> seed_dev) {
+              c10::optional<at::Tensor> seed_dev, c10::optional<at::Tensor> key_bits,
+              c10::optional<at::Tensor> out_lo) {
   TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == 3 * heads * 64, "qkv: [B, T, 3 * heads * 64]");
   const int64_t B = qkv.size(0), T = qkv.size(1);
   TORCH_CHECK(gk::attn_supported((int)T, 64), "attn: T must be a multiple of 128");
@@ -1797,13 +1815,15 @@ void attn_fwd(at::Tensor qkv, at::Tensor out, at::Tensor lse, int64_t heads, dou
   check_attn(out, "out", B * T, heads * 64);
   check_attn_f32(lse, "lse", B * heads * T);
   TORCH_CHECK(p >= 0.0 && p < 1.0, "attn: dropout p in [0, 1)");
+  const uint32_t* kb = key_bits_ptr(key_bits, qkv, B, T);
   c10::DeviceGuard guard(qkv.device());
   gk::attn_fwd(qkv.data_ptr(), out.data_ptr(), lse.data_ptr<float>(), (int)B, (int)T, (int)heads, (float)p,
-               (uint32_t)seed, seed_word(seed_dev), cur_stream(qkv));
+               (uint32_t)seed, seed_word(seed_dev), kb, out_lo_ptr(out_lo, kb, B * T, heads * 64), cur_stream(qkv));
 }
 
 void attn_bwd(at::Tensor qkv, at::Tensor out, at::Tensor dout, at::Tensor lse, at::Tensor delta, at::Tensor dqkv,
-              int64_t heads, double p, int64_t seed, c10::optional<at::Tensor> seed_dev) {
+              int64_t heads, double p, int64_t seed, c10::optional<at::Tensor> seed_dev,
+              c10::optional<at::Tensor> key_bits, c10::optional<at::Tensor> out_lo) {
   TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == 3 * heads * 64, "qkv: [B, T, 3 * heads * 64]");
   const int64_t B = qkv.size(0), T = qkv.size(1);
   TORCH_CHECK(gk::attn_supported((int)T, 64), "attn: T must be a multiple of 128");
@@ -1813,10 +1833,11 @@ void attn_bwd(at::Tensor qkv, at::Tensor out, at::Tensor dout, at::Tensor lse, a
   check_attn(dout, "dout", B * T, heads * 64);
   check_attn_f32(lse, "lse", B * heads * T);
   check_attn_f32(delta, "delta", B * heads * T);
+  const uint32_t* kb = key_bits_ptr(key_bits, qkv, B, T);
   c10::DeviceGuard guard(qkv.device());
   gk::attn_bwd(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr<float>(), delta.data_ptr<float>(),
-               dqkv.data_ptr(), (int)B, (int)T, (int)heads, (float)p, (uint32_t)seed, seed_word(seed_dev),
-               cur_stream(qkv));
+               dqkv.data_ptr(), (int)B, (int)T, (int)heads, (float)p, (uint32_t)seed, seed_word(seed_dev), kb,
+               out_lo_ptr(out_lo, kb, B * T, heads * 64), cur_stream(qkv));
 }
 
 void check_attn32(const at::Tensor& t, const char* name, int64_t rows, int64_t cols) {
@@ -1826,7 +1847,7 @@ void check_attn32(const at::Tensor& t, const char* name, int64_t rows, int64_t c
 }
 
 void attn_f32_fwd(at::Tensor qkv, at::Tensor out, at::Tensor lse, int64_t heads, double p, int64_t seed,
-                  c10::optional<at::Tensor> seed_dev) {
+                  c10::optional<at::Tensor> seed_dev, c10::optional<at::Tensor> key_bits) {
   TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == 3 * heads * 64, "qkv: [B, T, 3 * heads * 64]");
   const int64_t B = qkv.size(0), T = qkv.size(1);
   TORCH_CHECK(gk::attn_f32_supported((int)T, 64), "attn_f32: T must be a multiple of 128");
@@ -1835,13 +1856,15 @@ void attn_f32_fwd(at::Tensor qkv, at::Tensor out, at::Tensor lse, int64_t heads,
   check_attn_f32(lse, "lse", B * heads * T);
   TORCH_CHECK(p >= 0.0 && p < 1.0, "attn: dropout p in [0, 1)");
   TORCH_CHECK(B * heads * T * (T / 2) < (int64_t(1) << 32), "attn: dropout hash index must fit 32 bits");
+  const uint32_t* kb = key_bits_ptr(key_bits, qkv, B, T);
   c10::DeviceGuard guard(qkv.device());
   gk::attn_f32_fwd(qkv.data_ptr<float>(), out.data_ptr<float>(), lse.data_ptr<float>(), (int)B, (int)T, (int)heads,
-                   (float)p, (uint32_t)seed, seed_word(seed_dev), cur_stream(qkv));
+                   (float)p, (uint32_t)seed, seed_word(seed_dev), kb, cur_stream(qkv));
 }
 
 void attn_f32_bwd(at::Tensor qkv, at::Tensor out, at::Tensor dout, at::Tensor lse, at::Tensor delta, at::Tensor dqkv,
-                  int64_t heads, double p, int64_t seed, c10::optional<at::Tensor> seed_dev) {
+                  int64_t heads, double p, int64_t seed, c10::optional<at::Tensor> seed_dev,
+                  c10::optional<at::Tensor> key_bits) {
   TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == 3 * heads * 64, "qkv: [B, T, 3 * heads * 64]");
   const int64_t B = qkv.size(0), T = qkv.size(1);
   TORCH_CHECK(gk::attn_f32_supported((int)T, 64), "attn_f32: T must be a multiple of 128");
@@ -1851,10 +1874,28 @@ void attn_f32_bwd(at::Tensor qkv, at::Tensor out, at::Tensor dout, at::Tensor ls
   check_attn32(dout, "dout", B * T, heads * 64);
   check_attn_f32(lse, "lse", B * heads * T);
   check_attn_f32(delta, "delta", B * heads * T);
+  const uint32_t* kb = key_bits_ptr(key_bits, qkv, B, T);
   c10::DeviceGuard guard(qkv.device());
   gk::attn_f32_bwd(qkv.data_ptr<float>(), out.data_ptr<float>(), dout.data_ptr<float>(), lse.data_ptr<float>(),
                    delta.data_ptr<float>(), dqkv.data_ptr<float>(), (int)B, (int)T, (int)heads, (float)p,
-                   (uint32_t)seed, seed_word(seed_dev), cur_stream(qkv));
+                   (uint32_t)seed, seed_word(seed_dev), kb, cur_stream(qkv));
+}
+
+// [B, T] key mask (nonzero = valid; any 1-, 2-, 4- or 8-byte dtype) -> packed bits int32 [B, T / 32]
+void attn_pack_key_mask(at::Tensor mask, at::Tensor bits) {
+  TORCH_CHECK(mask.is_cuda() && mask.dim() == 2 && mask.is_contiguous(), "mask: contiguous GPU [B, T]");
+  const int64_t B = mask.size(0), T = mask.size(1);
+  TORCH_CHECK(T % 32 == 0, "mask: T must be a multiple of 32");
+  TORCH_CHECK(B * T < (int64_t(1) << 31), "mask: B * T must be below 2^31");
+  TORCH_CHECK(bits.is_cuda() && bits.device() == mask.device() && bits.scalar_type() == at::kInt &&
+                  bits.is_contiguous() && bits.numel() == B * T / 32,
+              "bits: contiguous int32 [B, T / 32] on the mask's device");
+  const int64_t es = mask.element_size();
+  TORCH_CHECK(!mask.is_complex() && (es == 1 || es == 2 || es == 4 || es == 8), "mask: unsupported dtype");
+  if (B * T == 0) return;
+  c10::DeviceGuard guard(mask.device());
+  gk::attn_pack_key_mask(mask.data_ptr(), (int)es, mask.is_floating_point(),
+                         reinterpret_cast<uint32_t*>(bits.data_ptr<int32_t>()), (int)B, (int)T, cur_stream(mask));
 }
 
 void attn_dropout_mask(at::Tensor mask, int64_t B, int64_t heads, int64_t T, double p, int64_t seed,
@@ -2168,13 +2209,16 @@ TORCH_LIBRARY(gksgd, m) {
   m.def("bn_fin_state_bytes(int C) -> int", &bn_fin_state_bytes);
   m.def("attn_supported(int T, int D) -> bool",
         [](int64_t T, int64_t D) { return gk::attn_supported((int)T, (int)D); });
-  m.def("attn_fwd(Tensor qkv, Tensor(a!) out, Tensor(b!) lse, int heads, float p, int seed, Tensor? seed_dev=None) -> ()");
+  m.def("attn_fwd(Tensor qkv, Tensor(a!) out, Tensor(b!) lse, int heads, float p, int seed, Tensor? seed_dev=None, "
+        "Tensor? key_bits=None, Tensor(c!)? out_lo=None) -> ()");
+  m.def("attn_pack_key_mask(Tensor mask, Tensor(a!) bits) -> ()");
   m.def("attn_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, Tensor(a!) delta, Tensor(b!) dqkv, int heads, "
-        "float p, int seed, Tensor? seed_dev=None) -> ()");
+        "float p, int seed, Tensor? seed_dev=None, Tensor? key_bits=None, Tensor? out_lo=None) -> ()");
   m.def("attn_dropout_mask(Tensor(a!) mask, int B, int heads, int T, float p, int seed, Tensor? seed_dev=None) -> ()");
-  m.def("attn_f32_fwd(Tensor qkv, Tensor(a!) out, Tensor(b!) lse, int heads, float p, int seed, Tensor? seed_dev=None) -> ()");
+  m.def("attn_f32_fwd(Tensor qkv, Tensor(a!) out, Tensor(b!) lse, int heads, float p, int seed, Tensor? seed_dev=None, "
+        "Tensor? key_bits=None) -> ()");
   m.def("attn_f32_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, Tensor(a!) delta, Tensor(b!) dqkv, int heads, "
-        "float p, int seed, Tensor? seed_dev=None) -> ()");
+        "float p, int seed, Tensor? seed_dev=None, Tensor? key_bits=None) -> ()");
   m.def("attn_f32_supported(int T, int D) -> bool",
         [](int64_t T, int64_t D) { return gk::attn_f32_supported((int)T, (int)D); });
   m.def("add_ln_supported(int H) -> bool", &add_ln_supported);
@@ -2285,6 +2329,7 @@ TORCH_LIBRARY_IMPL(gksgd, CUDA, m) {
   m.impl("attn_fwd", &attn_fwd);
   m.impl("attn_bwd", &attn_bwd);
   m.impl("attn_dropout_mask", &attn_dropout_mask);
+  m.impl("attn_pack_key_mask", &attn_pack_key_mask);
   m.impl("attn_f32_fwd", &attn_f32_fwd);
   m.impl("attn_f32_bwd", &attn_f32_bwd);
   m.impl("add_ln_forward", &add_ln_forward);

@@ -42,9 +42,22 @@
 // Dropout: keep(query, key) = half (key & 1) of hash(seed, (bh*T + q)*T/2 +
 // key/2) >= round(p * 65536), in all three kernels and attn_dropout_mask (for
 // tests); the mask is regenerated, never stored.
+//
+// Key-padding mask (MASK instantiations, attn_mask.h): packed valid bits per
+// (batch, key); masked keys get the score -inf, so P is exactly 0, lse runs
+// over the valid keys, and dK / dV of masked keys are written as zeros.  The
+// forward and the dQ kernel skip the arithmetic of key tiles without a valid
+// key and stop at the last tile that has one; the dK/dV kernel returns early
+// for 128 masked keys.  Every skip is uniform over the workgroup (or, inside
+// the dK/dV loop, leaves the wave on its barriers and staging duty).  The
+// masked forward can also store what the bf16 rounding of the output dropped
+// (out_lo), which the dQ kernel adds back for delta = rowsum(dO * O): rows
+// with few valid keys have concentrated P, where dP and delta nearly cancel.
+// The MASK = false instantiations are the code without any of this.
 #include "common.h"
 #include "gk_kernels.h"
 #include "mfma_util.h"
+#include "attn_mask.h"
 
 namespace gk {
 namespace {
@@ -156,6 +169,15 @@ __device__ __forceinline__ void store4(uint16_t* p, const f32x4& v, float s) {
   *reinterpret_cast<uint2*>(p) = make_uint2(pack_bf16x2(v[0] * s, v[1] * s), pack_bf16x2(v[2] * s, v[3] * s));
 }
 
+// what store4 rounds away, v * s - bf16(v * s), as bf16
+__device__ __forceinline__ void store4_lo(uint16_t* p, const f32x4& v, float s) {
+  const float x[4] = {v[0] * s, v[1] * s, v[2] * s, v[3] * s};
+  const uint32_t h0 = pack_bf16x2(x[0], x[1]), h1 = pack_bf16x2(x[2], x[3]);
+  *reinterpret_cast<uint2*>(p) =
+      make_uint2(pack_bf16x2(x[0] - __uint_as_float(h0 << 16), x[1] - __uint_as_float(h0 & 0xffff0000u)),
+                 pack_bf16x2(x[2] - __uint_as_float(h1 << 16), x[3] - __uint_as_float(h1 & 0xffff0000u)));
+}
+
 __device__ __forceinline__ float bf2f(short v) { return __uint_as_float((uint32_t)(uint16_t)v << 16); }
 
 // x * s rounded back to bf16 (the pre-scaled resident operand)
@@ -181,6 +203,10 @@ struct AttnArgs {
   float dscale;       // 1 / (1 - p_effective)
   uint32_t thr;       // drop threshold on 16 hash bits
   uint32_t seed;
+  const uint32_t* key_bits;   // optional [B, T / 32] valid-key bits (attn_mask.h), MASK kernels only
+  // optional, MASK kernels only: what the bf16 rounding of the output dropped, out_lo = bf16(O - out)
+  // [B, T, H, 64], written by the forward and added back by the dQ kernel for delta
+  uint16_t* out_lo;
   // optional replay word (graph capture): the effective seed mixes it in, so
   // a replayed step draws a fresh mask while forward and backward of one
   // replay read the same word
@@ -196,8 +222,9 @@ __device__ __forceinline__ uint32_t eff_seed(const AttnArgs& a) {
 // forward: one workgroup = 4 waves x 32 queries of one (batch, head); K/V
 // tiles of 64 keys in a 3-deep LDS ring
 // ---------------------------------------------------------------------------
-template <bool DROP>
-__global__ void __launch_bounds__(64 * kAW, 2) attn_fwd_kernel(AttnArgs a) {
+// (MASK: held to the 3 workgroups per CU that the unmasked forward's register count already allows)
+template <bool DROP, bool MASK>
+__global__ void __launch_bounds__(64 * kAW, MASK ? 3 : 2) attn_fwd_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(1024))) char smem[kStages * 2 * kTileB];
   const uint32_t seed = DROP ? eff_seed(a) : 0u;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, g = lane >> 4;
@@ -206,6 +233,7 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_fwd_kernel(AttnArgs a) {
   const int blk = xcd_block();
   const int bh = blk / nqb, qb = blk - bh * nqb;
   const int b = bh / H, h = bh - b * H;
+  const uint32_t* kbits = MASK ? a.key_bits + (int64_t)b * (T >> 5) : nullptr;
   const int64_t ld = 3LL * H * kHD;
   const uint16_t* base = a.qkv + (int64_t)b * T * ld;
   const int q0 = qb * kRows + wave * 32;
@@ -213,7 +241,8 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_fwd_kernel(AttnArgs a) {
   DmaSrc dma;
   dma.init(base + (int64_t)(H + h) * kHD, ld, base + (int64_t)(2 * H + h) * kHD, ld, wave, lane);
   const int64_t tstep = kKT * ld;
-  const int nt = T / kKT;
+  // MASK: stop after the last tile with a valid key (0 tiles: an empty sequence)
+  const int nt = MASK ? mask_tiles(kbits, T >> 5, lane) : T / kKT;
 
   bf16x8 qf[2][2];
 #pragma unroll
@@ -243,22 +272,46 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_fwd_kernel(AttnArgs a) {
   const uint32_t lbase = lds_addr(smem);
 
   int cur = 0, pre = 2;   // ring slots of tile t and of tile t + 2
+  bool started = false;   // MASK: a tile with a valid key has been seen
   for (int t = 0; t < nt; ++t) {
+    uint32_t w0 = ~0u, w1 = ~0u;   // valid bits of the tile's 64 keys (workgroup-uniform)
+    if (MASK) {
+      w0 = kbits[2 * t];
+      w1 = kbits[2 * t + 1];
+    }
     wait_tile<kPieces>(t + 1 >= nt);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     if (t + 2 < nt) dma.issue((t + 2) * tstep, (t + 2) * tstep, lds + pre * 2 * kTileB, wave);
+    if (MASK && (w0 | w1) == 0u) {   // no valid key: the ring moves on, the arithmetic is skipped
+      cur = ring_next(cur);
+      pre = ring_next(pre);
+      continue;
+    }
     const char* Ks = smem + cur * 2 * kTileB;
 
-    // S^T - m (log2 units), the running max as the initial accumulator
+    // S^T - m (log2 units), the running max as the initial accumulator (MASK:
+    // -inf for a masked key, which the MFMA carries through; set before the
+    // operand reads so that the tile's arithmetic stays one scheduling region)
     f32x4 s[2][4];
+    if (MASK) {
+#pragma unroll
+      for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt) s[qt][kt] = splat4(-m[qt]);
+      if ((w0 & w1) != ~0u) mask_scores_t(s, w0 >> (4 * g), w1 >> (4 * g));
+    }
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt) {
       const bf16x8 k0 = *reinterpret_cast<const bf16x8*>(Ks + aoff(16 * kt + li, g));
       const bf16x8 k1 = *reinterpret_cast<const bf16x8*>(Ks + aoff(16 * kt + li, 4 + g));
 #pragma unroll
-      for (int qt = 0; qt < 2; ++qt) s[qt][kt] = mfma(k1, qf[qt][1], mfma(k0, qf[qt][0], splat4(-m[qt])));
+      for (int qt = 0; qt < 2; ++qt)
+        s[qt][kt] = mfma(k1, qf[qt][1], mfma(k0, qf[qt][0], MASK ? s[qt][kt] : splat4(-m[qt])));
     }
+    // the first tile (MASK: the first with a valid key, where every row has a finite max)
+    const bool first = MASK ? !started : t == 0;
+    started = true;
 
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) {
@@ -266,10 +319,10 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_fwd_kernel(AttnArgs a) {
 #pragma unroll
       for (int kt = 1; kt < 4; ++kt)
         mx = fmaxf(mx, fmaxf(fmaxf(s[qt][kt][0], s[qt][kt][1]), fmaxf(s[qt][kt][2], s[qt][kt][3])));
-      if (t == 0 || __ballot(mx > kLazy) != 0) {   // wave-uniform, rare after the first tile
+      if (first || __ballot(mx > kLazy) != 0) {   // wave-uniform, rare after the first tile
         mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float d = t == 0 ? mx : fmaxf(mx, 0.f);
+        const float d = first ? mx : fmaxf(mx, 0.f);
         m[qt] += d;
         const float al = fexp2(-d);
         l[qt] *= al;
@@ -327,17 +380,25 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_fwd_kernel(AttnArgs a) {
       for (int qt = 0; qt < 2; ++qt) o[qt][dt] = mfma(vf[dt], pf[qt][1], o[qt][dt]);
   }
 
+  if (MASK && nt == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // tile 0's LDS-DMA
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
     float lt = l[qt];
     lt += __shfl_xor(lt, 16, 64);
     lt += __shfl_xor(lt, 32, 64);
     const int q = q0 + 16 * qt + li;
-    if (g == 0) a.lse[(int64_t)bh * T + q] = m[qt] + __log2f(lt);
-    const float inv = a.dscale / lt;
+    // MASK, a sequence without a valid key: out = 0 and lse = 0 (no tile was waited for)
+    const bool none = MASK && lt == 0.f;
+    if (g == 0) a.lse[(int64_t)bh * T + q] = none ? 0.f : m[qt] + __log2f(lt);
+    const float inv = none ? 0.f : a.dscale / lt;
     uint16_t* op = a.o + ((int64_t)b * T + q) * (H * kHD) + h * kHD + 4 * g;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) store4(op + 16 * dt, o[qt][dt], inv);
+    if (MASK && a.out_lo != nullptr) {
+      uint16_t* lp = a.out_lo + ((int64_t)b * T + q) * (H * kHD) + h * kHD + 4 * g;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) store4_lo(lp + 16 * dt, o[qt][dt], inv);
+    }
   }
 }
 
@@ -346,7 +407,7 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_fwd_kernel(AttnArgs a) {
 // tile S^T = c K Q^T - lse, dZ^T = V dO^T - delta', dS^T = P^T (dP^T - delta),
 // dQ^T += K^T dS^T
 // ---------------------------------------------------------------------------
-template <bool DROP>
+template <bool DROP, bool MASK>
 __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_dq_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(1024))) char smem[kStages * 2 * kTileB];
   const uint32_t seed = DROP ? eff_seed(a) : 0u;
@@ -356,6 +417,7 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_dq_kernel(AttnArgs a) {
   const int blk = xcd_block();
   const int bh = blk / nqb, qb = blk - bh * nqb;
   const int b = bh / H, h = bh - b * H;
+  const uint32_t* kbits = MASK ? a.key_bits + (int64_t)b * (T >> 5) : nullptr;
   const int64_t ld = 3LL * H * kHD, ldo = (int64_t)H * kHD;
   const uint16_t* base = a.qkv + (int64_t)b * T * ld;
   const int q0 = qb * kRows + wave * 32;
@@ -363,9 +425,14 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_dq_kernel(AttnArgs a) {
   DmaSrc dma;
   dma.init(base + (int64_t)(H + h) * kHD, ld, base + (int64_t)(2 * H + h) * kHD, ld, wave, lane);
   const int64_t tstep = kKT * ld;
-  const int nt = T / kKT;
+  // MASK: stop after the last tile with a valid key (0 tiles: an empty sequence)
+  const int nt = MASK ? mask_tiles(kbits, T >> 5, lane) : T / kKT;
 
   bf16x8 qf[2][2], df[2][2], of[2][2];
+  // MASK: the rounding residue of the output (zero without out_lo).  With few valid keys P is concentrated,
+  // dP and delta nearly cancel in dS = P (dP - delta), and delta from the bf16 output alone leaves a residue
+  // of 2^-9 |dO| |O| per query that adds up over the queries in dK and dQ
+  bf16x8 lf[2][2];
   float nlse[2], del[2], ndel[2];
   uint32_t hrow[2];
 #pragma unroll
@@ -377,6 +444,10 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_dq_kernel(AttnArgs a) {
       qf[qt][ks] = *reinterpret_cast<const bf16x8*>(base + h * kHD + (int64_t)q * ld + 32 * ks + 8 * g);
       df[qt][ks] = *reinterpret_cast<const bf16x8*>(a.dout + orow + 32 * ks + 8 * g);
       of[qt][ks] = *reinterpret_cast<const bf16x8*>(a.out + orow + 32 * ks + 8 * g);
+      if (MASK) {
+        lf[qt][ks] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+        if (a.out_lo != nullptr) lf[qt][ks] = *reinterpret_cast<const bf16x8*>(a.out_lo + orow + 32 * ks + 8 * g);
+      }
     }
     nlse[qt] = -a.lse[(int64_t)bh * T + q];
   }
@@ -390,7 +461,8 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_dq_kernel(AttnArgs a) {
     for (int ks = 0; ks < 2; ++ks) {
       qf[qt][ks] = scale_bf16x8(qf[qt][ks], a.sc);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) dsum = fmaf(bf2f(df[qt][ks][j]), bf2f(of[qt][ks][j]), dsum);
+      for (int j = 0; j < 8; ++j)
+        dsum = fmaf(bf2f(df[qt][ks][j]), MASK ? bf2f(of[qt][ks][j]) + bf2f(lf[qt][ks][j]) : bf2f(of[qt][ks][j]), dsum);
     }
     dsum += __shfl_xor(dsum, 16, 64);
     dsum += __shfl_xor(dsum, 32, 64);
@@ -412,15 +484,32 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_dq_kernel(AttnArgs a) {
 
   int cur = 0, pre = 2;   // ring slots of tile t and of tile t + 2
   for (int t = 0; t < nt; ++t) {
+    uint32_t w0 = ~0u, w1 = ~0u;   // valid bits of the tile's 64 keys (workgroup-uniform)
+    if (MASK) {
+      w0 = kbits[2 * t];
+      w1 = kbits[2 * t + 1];
+    }
     // the delta stores follow tile 1's pieces: drain everything on the first tile
     wait_tile<kPieces>(t == 0 || t + 1 >= nt);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     if (t + 2 < nt) dma.issue((t + 2) * tstep, (t + 2) * tstep, lds + pre * 2 * kTileB, wave);
+    if (MASK && (w0 | w1) == 0u) {   // no valid key: P = 0 for the whole tile
+      cur = ring_next(cur);
+      pre = ring_next(pre);
+      continue;
+    }
     const char* Ks = smem + cur * 2 * kTileB;
     const char* Vs = Ks + kTileB;
 
     f32x4 s[2][4], dz[2][4];
+    if (MASK) {   // masked keys: -inf through the MFMA, so P = exp2(-inf) and with it dS are exactly 0
+#pragma unroll
+      for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt) s[qt][kt] = splat4(nlse[qt]);
+      if ((w0 & w1) != ~0u) mask_scores_t(s, w0 >> (4 * g), w1 >> (4 * g));
+    }
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt) {
       const bf16x8 k0 = *reinterpret_cast<const bf16x8*>(Ks + aoff(16 * kt + li, g));
@@ -429,7 +518,7 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_dq_kernel(AttnArgs a) {
       const bf16x8 v1 = *reinterpret_cast<const bf16x8*>(Vs + aoff(16 * kt + li, 4 + g));
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt) {
-        s[qt][kt] = mfma(k1, qf[qt][1], mfma(k0, qf[qt][0], splat4(nlse[qt])));
+        s[qt][kt] = mfma(k1, qf[qt][1], mfma(k0, qf[qt][0], MASK ? s[qt][kt] : splat4(nlse[qt])));
         dz[qt][kt] = mfma(v1, df[qt][1], mfma(v0, df[qt][0], splat4(ndel[qt])));
       }
     }
@@ -482,6 +571,7 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_dq_kernel(AttnArgs a) {
       for (int qt = 0; qt < 2; ++qt) dq[qt][dt] = mfma(kf[dt], pf[qt][1], dq[qt][dt]);
   }
 
+  if (MASK && nt == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // tile 0's LDS-DMA
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
     const int q = q0 + 16 * qt + li;
@@ -500,7 +590,7 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_dq_kernel(AttnArgs a) {
 // ---------------------------------------------------------------------------
 constexpr int kKvBuf = 2 * kTileB + 512;   // Q tile, dO tile, lse[64], delta[64]
 
-template <bool DROP>
+template <bool DROP, bool MASK>
 __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_kv_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(1024))) char smem[kStages * kKvBuf];
   const uint32_t seed = DROP ? eff_seed(a) : 0u;
@@ -515,6 +605,25 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_kv_kernel(AttnArgs a) {
   const float* lsep = a.lse + (int64_t)bh * T;
   const float* delp = a.delta + (int64_t)bh * T;
   const int k0 = kb * kRows + wave * 32;
+  uint32_t ww = ~0u;   // valid bits of this wave's 32 keys (constant for the whole kernel)
+  if (MASK) {
+    const uint32_t* kw = a.key_bits + (int64_t)b * (T >> 5) + 4 * kb;
+    ww = kw[__builtin_amdgcn_readfirstlane(wave)];
+    if ((kw[0] | kw[1] | kw[2] | kw[3]) == 0u) {
+      // 128 masked keys: their dK / dV are zeros; nothing was staged, no barrier is reached
+#pragma unroll
+      for (int kt = 0; kt < 2; ++kt) {
+        uint16_t* row = a.dqkv + ((int64_t)b * T + k0 + 16 * kt + li) * ld + 4 * g;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+          *reinterpret_cast<uint2*>(row + (int64_t)(H + h) * kHD + 16 * dt) = make_uint2(0u, 0u);
+          *reinterpret_cast<uint2*>(row + (int64_t)(2 * H + h) * kHD + 16 * dt) = make_uint2(0u, 0u);
+        }
+      }
+      return;
+    }
+  }
+  const bool vk[2] = {(bool)((ww >> li) & 1u), (bool)((ww >> (16 + li)) & 1u)};   // this lane's keys
   GK_LDS char* lds = (GK_LDS char*)smem;
   DmaSrc dma;
   dma.init(base + (int64_t)h * kHD, ld, a.dout + (int64_t)b * T * ldo + (int64_t)h * kHD, ldo, wave, lane);
@@ -570,6 +679,7 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_kv_kernel(AttnArgs a) {
     const uint32_t qb = lbase + cur * kKvBuf;
     cur = ring_next(cur);
     pre = ring_next(pre);
+    if (MASK && ww == 0u) continue;   // no valid key in this wave: dK = dV = 0, only barriers and staging
 
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
@@ -591,6 +701,14 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_kv_kernel(AttnArgs a) {
           s[qt][kt] = mfma(qa1, kf[kt][1], mfma(qa0, kf[kt][0], nl));
           dz[qt][kt] = mfma(da1, vf[kt][1], mfma(da0, vf[kt][0], nd));
         }
+      }
+      if (MASK && ww != ~0u) {   // masked keys: P = exp2(-inf) = 0, so dV and dK columns stay 0
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+          for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) s[qt][kt][r] = vk[kt] ? s[qt][kt][r] : -INFINITY;
       }
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt) {
@@ -681,6 +799,21 @@ __global__ void attn_dropout_mask_kernel(uint8_t* __restrict__ mask, int64_t npa
   }
 }
 
+// key mask [B, T] (elements of type E; nonzero once the bits of `ignore` --
+// a float's sign -- are cleared) -> valid bits [B, T / 32]: one wave per 64
+// keys, one ballot, two words
+template <typename E>
+__global__ void __launch_bounds__(256) attn_pack_key_mask_kernel(const E* __restrict__ mask, uint32_t* __restrict__ bits,
+                                                                 int T, int per_row, int nwaves, E ignore) {
+  const int wv = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (wv >= nwaves) return;
+  const int row = wv / per_row, k = (wv - row * per_row) * 64 + lane;
+  const bool valid = k < T && (mask[(int64_t)row * T + k] & (E)~ignore) != 0;
+  const uint64_t bal = __ballot(valid);
+  const int w = k >> 5;   // T % 32 == 0: lanes 0 and 32 write whole words
+  if ((lane & 31) == 0 && k < T) bits[(int64_t)row * (T >> 5) + w] = (uint32_t)(bal >> (lane & 32));
+}
+
 AttnArgs make_args(int T, int H, float p, uint32_t seed, const uint32_t* seed_dev) {
   AttnArgs a{};
   a.seed_dev = seed_dev;
@@ -701,19 +834,27 @@ AttnArgs make_args(int T, int H, float p, uint32_t seed, const uint32_t* seed_de
 bool attn_supported(int T, int D) { return D == kHD && T >= kRows && T % kRows == 0; }
 
 void attn_fwd(const void* qkv, void* out, float* lse, int B, int T, int H, float p, uint32_t seed,
-              const uint32_t* seed_dev, hipStream_t stream) {
+              const uint32_t* seed_dev, const uint32_t* key_bits, void* out_lo, hipStream_t stream) {
   AttnArgs a = make_args(T, H, p, seed, seed_dev);
+  a.out_lo = key_bits ? static_cast<uint16_t*>(out_lo) : nullptr;
   a.qkv = static_cast<const uint16_t*>(qkv);
   a.o = static_cast<uint16_t*>(out);
   a.lse = lse;
+  a.key_bits = key_bits;
   const dim3 grid((unsigned)(B * H * (T / kRows)));
-  if (a.thr) hipLaunchKernelGGL(attn_fwd_kernel<true>, grid, dim3(64 * kAW), 0, stream, a);
-  else hipLaunchKernelGGL(attn_fwd_kernel<false>, grid, dim3(64 * kAW), 0, stream, a);
+  if (key_bits) {
+    if (a.thr) hipLaunchKernelGGL((attn_fwd_kernel<true, true>), grid, dim3(64 * kAW), 0, stream, a);
+    else hipLaunchKernelGGL((attn_fwd_kernel<false, true>), grid, dim3(64 * kAW), 0, stream, a);
+  } else if (a.thr) hipLaunchKernelGGL((attn_fwd_kernel<true, false>), grid, dim3(64 * kAW), 0, stream, a);
+  else hipLaunchKernelGGL((attn_fwd_kernel<false, false>), grid, dim3(64 * kAW), 0, stream, a);
 }
 
 void attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int B,
-              int T, int H, float p, uint32_t seed, const uint32_t* seed_dev, hipStream_t stream) {
+              int T, int H, float p, uint32_t seed, const uint32_t* seed_dev, const uint32_t* key_bits,
+              const void* out_lo, hipStream_t stream) {
   AttnArgs a = make_args(T, H, p, seed, seed_dev);
+  a.key_bits = key_bits;
+  a.out_lo = key_bits ? static_cast<uint16_t*>(const_cast<void*>(out_lo)) : nullptr;
   a.qkv = static_cast<const uint16_t*>(qkv);
   a.out = static_cast<const uint16_t*>(out);
   a.dout = static_cast<const uint16_t*>(dout);
@@ -721,13 +862,41 @@ void attn_bwd(const void* qkv, const void* out, const void* dout, const float* l
   a.delta = delta;
   a.dqkv = static_cast<uint16_t*>(dqkv);
   const dim3 grid((unsigned)(B * H * (T / kRows)));
-  if (a.thr) {
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, grid, dim3(64 * kAW), 0, stream, a);
-    hipLaunchKernelGGL(attn_bwd_kv_kernel<true>, grid, dim3(64 * kAW), 0, stream, a);
+  if (key_bits) {
+    if (a.thr) {
+      hipLaunchKernelGGL((attn_bwd_dq_kernel<true, true>), grid, dim3(64 * kAW), 0, stream, a);
+      hipLaunchKernelGGL((attn_bwd_kv_kernel<true, true>), grid, dim3(64 * kAW), 0, stream, a);
+    } else {
+      hipLaunchKernelGGL((attn_bwd_dq_kernel<false, true>), grid, dim3(64 * kAW), 0, stream, a);
+      hipLaunchKernelGGL((attn_bwd_kv_kernel<false, true>), grid, dim3(64 * kAW), 0, stream, a);
+    }
+  } else if (a.thr) {
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<true, false>), grid, dim3(64 * kAW), 0, stream, a);
+    hipLaunchKernelGGL((attn_bwd_kv_kernel<true, false>), grid, dim3(64 * kAW), 0, stream, a);
   } else {
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, grid, dim3(64 * kAW), 0, stream, a);
-    hipLaunchKernelGGL(attn_bwd_kv_kernel<false>, grid, dim3(64 * kAW), 0, stream, a);
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<false, false>), grid, dim3(64 * kAW), 0, stream, a);
+    hipLaunchKernelGGL((attn_bwd_kv_kernel<false, false>), grid, dim3(64 * kAW), 0, stream, a);
   }
+}
+
+void attn_pack_key_mask(const void* mask, int elem_size, bool is_float, uint32_t* bits, int B, int T,
+                        hipStream_t stream) {
+  const int per_row = (T + 63) / 64, nwaves = B * per_row;
+  const dim3 grid((unsigned)((nwaves + 3) / 4)), block(256);
+  if (elem_size == 1)
+    hipLaunchKernelGGL(attn_pack_key_mask_kernel<uint8_t>, grid, block, 0, stream, static_cast<const uint8_t*>(mask),
+                       bits, T, per_row, nwaves, (uint8_t)0);
+  else if (elem_size == 2)
+    hipLaunchKernelGGL(attn_pack_key_mask_kernel<uint16_t>, grid, block, 0, stream,
+                       static_cast<const uint16_t*>(mask), bits, T, per_row, nwaves,
+                       (uint16_t)(is_float ? 0x8000u : 0u));
+  else if (elem_size == 4)
+    hipLaunchKernelGGL(attn_pack_key_mask_kernel<uint32_t>, grid, block, 0, stream,
+                       static_cast<const uint32_t*>(mask), bits, T, per_row, nwaves, is_float ? 0x80000000u : 0u);
+  else
+    hipLaunchKernelGGL(attn_pack_key_mask_kernel<uint64_t>, grid, block, 0, stream,
+                       static_cast<const uint64_t*>(mask), bits, T, per_row, nwaves,
+                       is_float ? 0x8000000000000000ull : 0ull);
 }
 
 void attn_dropout_mask(uint8_t* mask, int B, int H, int T, float p, uint32_t seed, const uint32_t* seed_dev,

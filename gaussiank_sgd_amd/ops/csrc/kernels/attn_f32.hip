@@ -32,9 +32,15 @@
 // reads of rows 4g + j (g = 0 and 1 land in disjoint bank halves).  Tiles are
 // staged by LDS-DMA (global_load_lds 16 B per lane; the swizzle is applied to
 // the source address), two stages deep.
+//
+// Key-padding mask (MASK instantiations), as attn.hip: masked keys score
+// -inf; the forward and the dQ kernel skip the arithmetic of key tiles without
+// a valid key and stop at the last tile that has one; the dK/dV kernel writes
+// zeros and returns for 128 masked keys.  MASK = false is the code without it.
 #include "common.h"
 #include "gk_kernels.h"
 #include "mfma_util.h"
+#include "attn_mask.h"
 
 namespace gk {
 namespace {
@@ -84,6 +90,7 @@ struct AttnF32Args {
   uint32_t thr;    // drop threshold on 16 hash bits
   uint32_t seed;
   const uint32_t* seed_dev;
+  const uint32_t* key_bits;   // optional [B, T / 32] valid-key bits (attn_mask.h), MASK kernels only
 };
 
 __device__ __forceinline__ uint32_t eff_seed(const AttnF32Args& a) {
@@ -118,7 +125,7 @@ __device__ __forceinline__ float ld1(const char* lds, uint32_t off) { return *re
 // ---------------------------------------------------------------------------
 // forward: 4 waves x 32 queries of one (batch, head); K / V tiles of 64 keys
 // ---------------------------------------------------------------------------
-template <bool DROP>
+template <bool DROP, bool MASK>
 __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Args a) {
   extern __shared__ __attribute__((aligned(1024))) char smem[];   // 2 stages x (K, V)
   const uint32_t seed = DROP ? eff_seed(a) : 0u;
@@ -137,10 +144,12 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Arg
   dk.init(base + (int64_t)(H + h) * kHD, ld, wave, lane);
   dv.init(base + (int64_t)(2 * H + h) * kHD, ld, wave, lane);
   const int64_t tstep = kKT * ld;
-  const int nt = T / kKT;
+  const uint32_t* kbits = MASK ? a.key_bits + (int64_t)b * (T >> 5) : nullptr;
 
   dk.issue(0, lds, wave);
   dv.issue(0, lds + kFTile, wave);
+  // MASK: stop after the last tile with a valid key (0 tiles: an empty sequence)
+  const int nt = MASK ? mask_tiles(kbits, T >> 5, lane) : T / kKT;
   f32x4 qf[2][4];
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt)
@@ -159,7 +168,13 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Arg
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) hrow[qt] = ((uint32_t)bh * T + q0 + 16 * qt + li) * (uint32_t)(T >> 1) + 2 * g;
 
+  bool started = false;   // MASK: a tile with a valid key has been seen
   for (int t = 0; t < nt; ++t) {
+    uint32_t w0 = ~0u, w1 = ~0u;   // valid bits of the tile's 64 keys (workgroup-uniform)
+    if (MASK) {
+      w0 = kbits[2 * t];
+      w1 = kbits[2 * t + 1];
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of tile t
     __builtin_amdgcn_s_barrier();                        // everyone's pieces; tile t - 1 consumed
     __builtin_amdgcn_sched_barrier(0);
@@ -170,6 +185,7 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Arg
       dk.issue((t + 1) * tstep, nx, wave);
       dv.issue((t + 1) * tstep, nx + kFTile, wave);
     }
+    if (MASK && (w0 | w1) == 0u) continue;   // no valid key: staged and waited for, no arithmetic
 
     // S^T - m (log2 units)
     f32x4 s[2][4];
@@ -177,6 +193,8 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Arg
     for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
       for (int kt = 0; kt < 4; ++kt) s[qt][kt] = splat4(-m[qt]);
+    // masked keys: -inf in the initial accumulator, which the MFMAs carry through
+    if (MASK && (w0 & w1) != ~0u) mask_scores_t(s, w0 >> (4 * g), w1 >> (4 * g));
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
@@ -185,6 +203,9 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Arg
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt) s[qt][kt] = mfma16(kv, qf[qt][c], s[qt][kt]);
       }
+    // the first tile (MASK: the first with a valid key, where every row has a finite max)
+    const bool first = MASK ? !started : t == 0;
+    started = true;
 
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) {
@@ -192,10 +213,10 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Arg
 #pragma unroll
       for (int kt = 1; kt < 4; ++kt)
         mx = fmaxf(mx, fmaxf(fmaxf(s[qt][kt][0], s[qt][kt][1]), fmaxf(s[qt][kt][2], s[qt][kt][3])));
-      if (t == 0 || __ballot(mx > kLazy) != 0) {
+      if (first || __ballot(mx > kLazy) != 0) {
         mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float d = t == 0 ? mx : fmaxf(mx, 0.f);
+        const float d = first ? mx : fmaxf(mx, 0.f);
         m[qt] += d;
         const float al = fexp2(-d);
         l[qt] *= al;
@@ -242,14 +263,17 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Arg
       }
   }
 
+  if (MASK && nt == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // tile 0's LDS-DMA
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
     float lt = l[qt];
     lt += __shfl_xor(lt, 16, 64);
     lt += __shfl_xor(lt, 32, 64);
     const int q = q0 + 16 * qt + li;
-    if (g == 0) a.lse[(int64_t)bh * T + q] = m[qt] + __log2f(lt);
-    const float inv = a.dscale / lt;
+    // MASK, a sequence without a valid key: out = 0 and lse = 0 (no tile was waited for)
+    const bool none = MASK && lt == 0.f;
+    if (g == 0) a.lse[(int64_t)bh * T + q] = none ? 0.f : m[qt] + __log2f(lt);
+    const float inv = none ? 0.f : a.dscale / lt;
     float* op = a.o + ((int64_t)b * T + q) * (H * kHD) + h * kHD + 4 * g;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<f32x4*>(op + 16 * dt) = o[qt][dt] * inv;
@@ -260,7 +284,7 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Arg
 // backward, dQ (+ delta = rowsum(dO * O)): per key tile S^T = c K Q^T - lse,
 // dZ^T = V dO^T - delta', dS^T = P^T (dP^T - delta), dQ^T += K^T dS^T
 // ---------------------------------------------------------------------------
-template <bool DROP>
+template <bool DROP, bool MASK>
 __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_dq_kernel(AttnF32Args a) {
   extern __shared__ __attribute__((aligned(1024))) char smem[];   // 2 stages x (K, V)
   const uint32_t seed = DROP ? eff_seed(a) : 0u;
@@ -279,10 +303,12 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_dq_kernel(AttnF32
   dk.init(base + (int64_t)(H + h) * kHD, ld, wave, lane);
   dv.init(base + (int64_t)(2 * H + h) * kHD, ld, wave, lane);
   const int64_t tstep = kKT * ld;
-  const int nt = T / kKT;
+  const uint32_t* kbits = MASK ? a.key_bits + (int64_t)b * (T >> 5) : nullptr;
 
   dk.issue(0, lds, wave);
   dv.issue(0, lds + kFTile, wave);
+  // MASK: stop after the last tile with a valid key (0 tiles: an empty sequence)
+  const int nt = MASK ? mask_tiles(kbits, T >> 5, lane) : T / kKT;
   f32x4 qf[2][4], df[2][4];
   float nlse[2], del[2], ndel[2];
   uint32_t hrow[2];
@@ -315,6 +341,11 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_dq_kernel(AttnF32
     for (int dt = 0; dt < 4; ++dt) dq[qt][dt] = splat4(0.f);
 
   for (int t = 0; t < nt; ++t) {
+    uint32_t w0 = ~0u, w1 = ~0u;   // valid bits of the tile's 64 keys (workgroup-uniform)
+    if (MASK) {
+      w0 = kbits[2 * t];
+      w1 = kbits[2 * t + 1];
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
@@ -325,6 +356,7 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_dq_kernel(AttnF32
       dk.issue((t + 1) * tstep, nx, wave);
       dv.issue((t + 1) * tstep, nx + kFTile, wave);
     }
+    if (MASK && (w0 | w1) == 0u) continue;   // no valid key: P = 0 for the whole tile
 
     f32x4 s[2][4], dz[2][4];
 #pragma unroll
@@ -334,6 +366,8 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_dq_kernel(AttnF32
         s[qt][kt] = splat4(nlse[qt]);
         dz[qt][kt] = splat4(ndel[qt]);
       }
+    // masked keys: -inf through the MFMAs, so P = exp2(-inf) and with it dS are exactly 0
+    if (MASK && (w0 & w1) != ~0u) mask_scores_t(s, w0 >> (4 * g), w1 >> (4 * g));
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt) {
 #pragma unroll
@@ -387,6 +421,7 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_dq_kernel(AttnF32
       }
   }
 
+  if (MASK && nt == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // tile 0's LDS-DMA
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
     const int q = q0 + 16 * qt + li;
@@ -404,7 +439,7 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_dq_kernel(AttnF32
 // ---------------------------------------------------------------------------
 constexpr int kKvStage = 2 * kFTile + 512;   // Q tile, dO tile, lse[64], delta[64]
 
-template <bool DROP>
+template <bool DROP, bool MASK>
 __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_kv_kernel(AttnF32Args a) {
   extern __shared__ __attribute__((aligned(1024))) char smem[];   // 2 x kKvStage
   const uint32_t seed = DROP ? eff_seed(a) : 0u;
@@ -420,6 +455,25 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_kv_kernel(AttnF32
   const float* lsep = a.lse + (int64_t)bh * T;
   const float* delp = a.delta + (int64_t)bh * T;
   const int k0 = kb * kRows + wave * 32;
+  uint32_t ww = ~0u;   // valid bits of this wave's 32 keys (constant for the whole kernel)
+  if (MASK) {
+    const uint32_t* kw = a.key_bits + (int64_t)b * (T >> 5) + 4 * kb;
+    ww = kw[wave];
+    if ((kw[0] | kw[1] | kw[2] | kw[3]) == 0u) {
+      // 128 masked keys: their dK / dV are zeros; nothing was staged, no barrier is reached
+#pragma unroll
+      for (int kt = 0; kt < 2; ++kt) {
+        float* row = a.dqkv + ((int64_t)b * T + k0 + 16 * kt + li) * ld + 4 * g;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+          *reinterpret_cast<f32x4*>(row + (int64_t)(H + h) * kHD + 16 * dt) = splat4(0.f);
+          *reinterpret_cast<f32x4*>(row + (int64_t)(2 * H + h) * kHD + 16 * dt) = splat4(0.f);
+        }
+      }
+      return;
+    }
+  }
+  const bool vk[2] = {(bool)((ww >> li) & 1u), (bool)((ww >> (16 + li)) & 1u)};   // this lane's keys
   GK_LDS char* lds = (GK_LDS char*)smem;
   TileDma dq, dd;
   dq.init(base + (int64_t)h * kHD, ld, wave, lane);
@@ -460,6 +514,7 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_kv_kernel(AttnF32
     const char* Ds = Qs + kFTile;
     const float* Ls = reinterpret_cast<const float*>(Qs + 2 * kFTile);
     if (t + 1 < nt) stage(t + 1, (t + 1) & 1);
+    if (MASK && ww == 0u) continue;   // no valid key in this wave: dK = dV = 0, only barriers and staging
 
 #pragma unroll 1
     for (int qt = 0; qt < 4; ++qt) {   // not unrolled: one 16-query tile's operands live at a time
@@ -482,6 +537,12 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_kv_kernel(AttnF32
           s[kt] = mfma16(qv, kf[kt][c], s[kt]);
           dz[kt] = mfma16(ov, vf[kt][c], dz[kt]);
         }
+      }
+      if (MASK && ww != ~0u) {   // masked keys: P = exp2(-inf) = 0, so dV and dK columns stay 0
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) s[kt][r] = vk[kt] ? s[kt][r] : -INFINITY;
       }
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt) {
@@ -558,18 +619,23 @@ void launch(K kern, int nblocks, int lds, const AttnF32Args& a, hipStream_t stre
 bool attn_f32_supported(int T, int D) { return D == kHD && T >= kRows && T % kRows == 0; }
 
 void attn_f32_fwd(const float* qkv, float* out, float* lse, int B, int T, int H, float p, uint32_t seed,
-                  const uint32_t* seed_dev, hipStream_t stream) {
+                  const uint32_t* seed_dev, const uint32_t* key_bits, hipStream_t stream) {
   AttnF32Args a = make_args(T, H, p, seed, seed_dev);
   a.qkv = qkv;
   a.o = out;
   a.lse = lse;
+  a.key_bits = key_bits;
   const int nb = B * H * (T / kRows);
-  if (a.thr) launch(attn_f32_fwd_kernel<true>, nb, 4 * kFTile, a, stream);
-  else launch(attn_f32_fwd_kernel<false>, nb, 4 * kFTile, a, stream);
+  if (key_bits) {
+    if (a.thr) launch(attn_f32_fwd_kernel<true, true>, nb, 4 * kFTile, a, stream);
+    else launch(attn_f32_fwd_kernel<false, true>, nb, 4 * kFTile, a, stream);
+  } else if (a.thr) launch(attn_f32_fwd_kernel<true, false>, nb, 4 * kFTile, a, stream);
+  else launch(attn_f32_fwd_kernel<false, false>, nb, 4 * kFTile, a, stream);
 }
 
 void attn_f32_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* delta, float* dqkv,
-                  int B, int T, int H, float p, uint32_t seed, const uint32_t* seed_dev, hipStream_t stream) {
+                  int B, int T, int H, float p, uint32_t seed, const uint32_t* seed_dev, const uint32_t* key_bits,
+                  hipStream_t stream) {
   AttnF32Args a = make_args(T, H, p, seed, seed_dev);
   a.qkv = qkv;
   a.out = out;
@@ -577,13 +643,22 @@ void attn_f32_bwd(const float* qkv, const float* out, const float* dout, const f
   a.lse = const_cast<float*>(lse);
   a.delta = delta;
   a.dqkv = dqkv;
+  a.key_bits = key_bits;
   const int nb = B * H * (T / kRows);
-  if (a.thr) {
-    launch(attn_f32_bwd_dq_kernel<true>, nb, 4 * kFTile, a, stream);
-    launch(attn_f32_bwd_kv_kernel<true>, nb, 2 * kKvStage, a, stream);
+  if (key_bits) {
+    if (a.thr) {
+      launch(attn_f32_bwd_dq_kernel<true, true>, nb, 4 * kFTile, a, stream);
+      launch(attn_f32_bwd_kv_kernel<true, true>, nb, 2 * kKvStage, a, stream);
+    } else {
+      launch(attn_f32_bwd_dq_kernel<false, true>, nb, 4 * kFTile, a, stream);
+      launch(attn_f32_bwd_kv_kernel<false, true>, nb, 2 * kKvStage, a, stream);
+    }
+  } else if (a.thr) {
+    launch(attn_f32_bwd_dq_kernel<true, false>, nb, 4 * kFTile, a, stream);
+    launch(attn_f32_bwd_kv_kernel<true, false>, nb, 2 * kKvStage, a, stream);
   } else {
-    launch(attn_f32_bwd_dq_kernel<false>, nb, 4 * kFTile, a, stream);
-    launch(attn_f32_bwd_kv_kernel<false>, nb, 2 * kKvStage, a, stream);
+    launch(attn_f32_bwd_dq_kernel<false, false>, nb, 4 * kFTile, a, stream);
+    launch(attn_f32_bwd_kv_kernel<false, false>, nb, 2 * kKvStage, a, stream);
   }
 }
 

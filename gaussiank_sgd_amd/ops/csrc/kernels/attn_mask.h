@@ -1,0 +1,44 @@
+// Key-padding mask of the fused attention kernels (attn.hip, attn_f32.hip).
+//
+// key_bits: uint32 [B, T / 32]; bit j of word w of a sequence is key 32 w + j,
+// set = valid.  A 64-key tile is two words, the 128 keys of a dK/dV workgroup
+// four; both are read through a workgroup-uniform address.
+#pragma once
+#include "common.h"
+#include "mfma_util.h"
+
+namespace gk {
+
+// one past the last 64-key tile of a sequence that holds a valid key (0: the
+// sequence has none).  kb: the sequence's nw = T / 32 words.  Every lane of
+// every wave reads the same words, so the result is workgroup-uniform.
+__device__ __forceinline__ int mask_tiles(const uint32_t* kb, int nw, int lane) {
+  int last = -1;   // last non-zero word
+  for (int c = 0; c < nw; c += 64) {
+    const uint32_t v = c + lane < nw ? kb[c + lane] : 0u;
+    const uint64_t bal = __ballot(v != 0u);
+    if (bal) last = c + 63 - __builtin_clzll(bal);
+  }
+  return (last >> 1) + 1;
+}
+
+// scores of one 64-key tile in the transposed layout of the forward and dQ
+// kernels (the lane holds keys 16 kt + 4g + r): -inf where the key's bit is
+// clear.  lo / hi: the tile's two mask words shifted right by 4g, so every bit
+// position is a constant.  min(s, +-inf) with the sign taken from the bit: a
+// few in-place integer ops per score and no compare masks -- the select form
+// (32 lane masks alive at once) cost the bf16 forward its third workgroup per CU.
+__device__ __forceinline__ void mask_scores_t(f32x4 (&s)[2][4], uint32_t lo, uint32_t hi) {
+#pragma unroll
+  for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const uint32_t w = kt < 2 ? lo : hi;
+        const uint32_t neg = ((w << (31 - (16 * (kt & 1) + r))) & 0x80000000u) ^ 0x80000000u;   // sign set = masked
+        s[qt][kt][r] = fminf(s[qt][kt][r], __uint_as_float(0x7f800000u | neg));
+      }
+}
+
+}  // namespace gk
