@@ -99,6 +99,7 @@ def main() -> int:
         }
         impl = {}
         if args.ours and C % 64 == 0 and K % 64 == 0:
+            from gaussiank_sgd_amd.ops import autotune
             from gaussiank_sgd_amd.ops import conv1x1 as cv
             wo = torch.zeros(K, C, k, k, device=dev, dtype=torch.float32).contiguous(memory_format=torch.channels_last)
             cases = {
@@ -109,8 +110,8 @@ def main() -> int:
             for name, (fn, _) in cases.items():
                 fn()
             geo = (N, C, H, W, K, k, s)
-            impl = {"fwd": cv._choices.get(("fwd",) + geo + (True,)), "dgrad": cv._choices.get(("dgrad",) + geo),
-                    "wgrad": cv._choices.get(("wgrad",) + geo)}
+            impl = {"fwd": autotune.choice(("fwd",) + geo + (True,)), "dgrad": autotune.choice(("dgrad",) + geo),
+                    "wgrad": autotune.choice(("wgrad",) + geo)}
         if C == 3:
             del cases["dgrad"]   # the stem's input (the image batch) needs no gradient in training
         for name, (fn, nbytes) in cases.items():

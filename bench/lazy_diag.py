@@ -11,7 +11,7 @@ import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
 from gaussiank_sgd_amd.models.resnet_imagenet import resnet50  # noqa: E402
-from gaussiank_sgd_amd.ops import conv1x1  # noqa: E402
+from gaussiank_sgd_amd.ops import autotune  # noqa: E402
 from gaussiank_sgd_amd.ops.bn import BNAct  # noqa: E402
 
 CL = torch.channels_last
@@ -49,6 +49,6 @@ for n in ref:
     errs = [(runs[k][n] - ref[n]).abs().max().item() / sc for k in runs]
     flag = " <<<" if max(errs[1:]) > 5 * errs[0] + 1e-4 else ""
     print("%-30s " % n + " ".join("%9.2e" % e for e in errs) + flag)
-for k, v in conv1x1.tuned_choices().items():
+for k, v in autotune.tuned_choices().items():
     if k[-1] == "lz":
         print("choice", json.dumps(list(k)), v)

@@ -2,7 +2,7 @@
 """Grad-weight (TN) GEMM configurations vs hipBLASLt / MIOpen on the shapes
 that dominate BERT-base (M = 32 x 512 tokens) and ResNet-50 bs512.
 
-For each shape: every gemm_tn / conv_tn config of ops/conv1x1._TN_CFGS,
+For each shape: every gemm_tn / conv_tn config of ops/autotune.py tn_cfgs (bf16),
 hipBLASLt bf16 -> fp32 with beta = 1 (``torch.addmm(out_dtype=float32)``)
 for the linears, MIOpen for the convolutions; achieved TFLOP/s and % of the
 2.5 PFLOP/s dense bf16 peak.
@@ -38,6 +38,7 @@ def main():
     ap.add_argument("--json-out", default=None)
     args = ap.parse_args()
     from gaussiank_sgd_amd import ops
+    from gaussiank_sgd_amd.ops import autotune
     from gaussiank_sgd_amd.ops import conv1x1 as cv
     assert ops.load()
     g = torch.ops.gksgd
@@ -50,7 +51,7 @@ def main():
         out = torch.zeros(N, K, device=dev)
         flops = 2.0 * M * N * K
         res = {}
-        for c, sp in cv._TN_CFGS:
+        for c, sp in autotune.tn_cfgs(torch.bfloat16):
             try:
                 res["hip %d/%d" % (c, sp)] = timeit(lambda c=c, sp=sp: g.gemm_tn_acc(dy, x, out, c, sp))
             except RuntimeError as e:
@@ -74,7 +75,7 @@ def main():
         z = torch.zeros(256, dtype=torch.bfloat16, device=dev)
         flops = 2.0 * N * OH * OH * K * C * k * k
         res = {}
-        for c, sp in cv._TN_CFGS:
+        for c, sp in autotune.tn_cfgs(torch.bfloat16):
             try:
                 if k == 1 and s == 1:
                     DY, X = cv._rows(dy), cv._rows(x)

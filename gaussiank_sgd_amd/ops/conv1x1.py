@@ -16,8 +16,10 @@ v_mfma_f32_16x16x4_f32: exact fp32 products, fp32 accumulation).
 
 For every distinct (direction, geometry) the first call times a small set of
 kernel configurations *and* the MIOpen convolution with HIP events and keeps
-the fastest (``GKSGD_GEMM_TUNE=0`` skips the search and uses the HIP
-kernel's heuristic default; ``GKSGD_FASTCONV=0`` disables the path).  The
+the fastest (ops/autotune.py ``pick``, which also owns the choice table, the
+fp32 matmul mode and the GEMM candidate lists; ``GKSGD_GEMM_TUNE=0`` skips
+the search and uses the HIP kernel's heuristic default; ``GKSGD_FASTCONV=0``
+disables the path).  This module keeps the convolution-only policy.  The
 grad-weight kernels add their fp32 result straight into the optimizer's
 gradient arena (float atomics) when the module is on the bf16-shadow path
 (``parallel/shadow.py``), so no bf16 weight gradient is materialised.
@@ -29,30 +31,24 @@ Reference parity: the reference's ResNets use ``nn.Conv2d``
 from __future__ import annotations
 
 import os
-from typing import Callable, Dict, List, Tuple
+from itertools import product
+from typing import Dict
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import autotune
 from . import load
 from . import streams
 from . import weight_prep
+from .autotune import (X6, f32_matmul, load_choices, save_choices, set_f32_matmul,  # noqa: F401  (re-exported)
+                       tuned_choices, tuning_log)
 
 _CL = torch.channels_last
-_TUNE = os.environ.get("GKSGD_GEMM_TUNE", "1") != "0"
 _ENABLED = os.environ.get("GKSGD_FASTCONV", "1") != "0"
-_choices: Dict[tuple, tuple] = {}
-# candidates that are this package's own kernels; a vendor-library choice
-# (MIOpen / hipBLASLt) has to beat the best of them by more than this fraction
-# of its time (GKSGD_GK_MARGIN, default 5%: the fp32 implicit-GEMM kernels
-# trail MIOpen's by 1-5% on some 3x3 shapes -- kept, so the fp32 step runs on
-# code this package owns; 0 = fastest wins)
-_OWN = ("hip", "w3", "mat", "wino", "wx6")
-_GK_MARGIN = float(os.environ.get("GKSGD_GK_MARGIN", "0.05"))
 # convolution bias gradients through the fused column pass (GKSGD_CONV_BIAS_COLSUM=0: torch's reduction)
 _BIAS_COLSUM = os.environ.get("GKSGD_CONV_BIAS_COLSUM", "1") != "0"
-_timings: Dict[tuple, list] = {}      # key -> [(tag, ms or error)] of the search
 # fp32 3x3 stride-1 forward / grad-input: Winograd F(2x2, 3x3) candidates
 # (winograd.hip, 2.25x fewer MFMA FLOPs); GKSGD_WINO=0 leaves them out.  Their
 # autotune keys carry a "wino" tag so choices cached before they existed are
@@ -60,111 +56,6 @@ _timings: Dict[tuple, list] = {}      # key -> [(tag, ms or error)] of the searc
 _WINO = os.environ.get("GKSGD_WINO", "1") != "0"
 _FORCE = os.environ.get("GKSGD_CONV_FORCE", "")
 _WINO_GRIDS = (0, 1 << 20)
-# candidate kernel configurations: the digits of a cfg word are fields, see csrc/kernels/gemm_cfg.h
-_NT_CFGS = [1, 2, 3, 4, 11, 13, 21, 22, 23, 24, 111, 113, 121, 122, 123, 124, 25, 26, 27, 125, 126, 127,
-            211, 212, 213, 214, 221, 222, 223, 224]   # 2xx: four LDS stages (more bytes in flight)
-# grid override: 0 = persistent (about two blocks per CU), else a fixed block count
-_NT_GRIDS = (0, 512, 1 << 20)
-_TN_CFGS = [(c, s) for c in (1, 2, 3, 4, 5, 6, 7, 8, 21, 22, 23, 24, 27, 9, 29, 101, 121, 102, 122) for s in (0, 128)]
-# fp32: 64x64 wave tiles (NT tiles 5-7 map onto them) and, cfg + 1000, 32x64 wave tiles
-# (twice the waves: the small-M layers of small batches, e.g. the reference's bs32)
-_NT_CFGS_F32 = [1, 2, 3, 4, 7, 11, 12, 13, 14, 21, 22, 23, 24, 101, 102, 103, 104, 201, 202, 203, 204,
-                1001, 1002, 1003, 1004, 1005, 1006, 1007, 1021, 1022, 1101, 1102, 1103]
-_TN_CFGS_F32 = [(c, s) for c in (1, 2, 3, 4, 5, 6, 7, 8, 9, 11, 12, 13, 14, 15, 16) for s in (0, 64)]
-# grad-weight of small-batch layers (pixel rows <= _TN_SMALL_M, e.g. ResNet-50 bs32): the default split
-# count (two rounds of block slots) trades partial-sum atomics against idle CUs; these let the tuner pick
-_TN_SMALL_M = 1 << 17
-_TN_SMALL_F32 = [(c, s) for c in (4, 5, 11, 14, 15) for s in (16, 32, 128)]
-
-
-# fp32 matmul algorithm (GKSGD_F32_MATMUL / set_f32_matmul):
-#   "native" -- fp32 operands on v_mfma_f32_16x16x4_f32 only;
-#   "bf16x6" -- the fp32 GEMM / implicit-GEMM candidates also include the bf16x6
-#   kernels (gemm_nt.h / gemm_tn_f32.h X6, cfg digit 100000): every fp32 operand split exactly
-#   into three bf16 parts, the six part products of order <= 2 accumulated in
-#   fp32 on v_mfma_f32_16x16x32_bf16 -- measured MORE accurate than the fp32
-#   MFMA against an fp64 reference on every ResNet-50 / BERT shape
-#   (bench/x6_probe.py, profiles/r05_x6_probe.json), so it is an fp32 algorithm,
-#   not a reduced precision; the tuner picks the faster kernel per shape.
-X6 = 100000
-_NT_CFGS_X6 = [c + X6 for c in (1, 2, 3, 4, 5, 6, 7, 12, 13, 101, 102, 103, 104, 105, 106, 107, 202, 203, 1001, 1002, 1003)]
-# register-staged bf16x6 row GEMMs (gemm_nt_x62.h gemm_nt_x62_kernel, cfg digit 200000; tiles 1-7):
-# plain row GEMMs only -- an implicit-GEMM / lazy / split-K call refuses them and the tuner moves on.
-# Digit 300000: the same kernels with B split into bf16 planes once per call by the binding
-# (split3_rows), no B split in the kernel: within +-3% of 200000, up to 8% faster on a few shapes (r5c33)
-_NT_CFGS_X62 = [2 * X6 + t for t in range(1, 8)] + [3 * X6 + t for t in range(1, 8)]
-# default bf16x6: the library, the trainers (dist_trainer --f32-matmul) and
-# bench.py all run the same fp32 GEMM family unless told otherwise
-_F32MM = os.environ.get("GKSGD_F32_MATMUL", "bf16x6")
-
-
-def set_f32_matmul(mode: str) -> str:
-    """Select the fp32 matmul algorithm ("native" or "bf16x6"); returns the
-    previous one.  Autotune keys carry the mode, so each mode is tuned once."""
-    global _F32MM
-    if mode not in ("native", "bf16x6"):
-        raise ValueError("f32 matmul mode must be 'native' or 'bf16x6', got %r" % (mode,))
-    prev, _F32MM = _F32MM, mode
-    return prev
-
-
-def f32_matmul() -> str:
-    return _F32MM
-
-
-def _x6() -> bool:
-    return _F32MM == "bf16x6"
-
-
-# register-staged bf16x6 grad-weight (gemm_tn_x62.h gemm_tn_x62_kernel, cfg digit 200000; tiles 1-8):
-# plain row form only -- an implicit-GEMM / lazy call refuses them and the tuner moves on
-_TN_CFGS_X62 = [(2 * X6 + t, sp) for t in (1, 2, 3, 4, 5, 6, 7, 8) for sp in (0, 64)]
-
-
-def _tn_cfgs(dt: torch.dtype) -> List[Tuple[int, int]]:
-    if dt == torch.float32:
-        # (_TN_CFGS_X62 measured no faster than the LDS-DMA bf16x6 grad-weight on any ResNet-50 /
-        # BERT shape, r5c27: not offered by default, GKSGD_TN_X62=1 adds them)
-        extra = _TN_CFGS_X62 if os.environ.get("GKSGD_TN_X62", "0") == "1" else []
-        return _TN_CFGS_F32 + ([(c + X6, sp) for c, sp in _TN_CFGS_F32] + extra if _x6() else [])
-    return _TN_CFGS
-
-
-def _nt_cfgs(dt: torch.dtype) -> List[int]:
-    if dt == torch.float32:
-        return _NT_CFGS_F32 + (_NT_CFGS_X6 + _NT_CFGS_X62 if _x6() else [])
-    return _NT_CFGS
-
-
-# fp32 split-K (cfg + 10000 S: S fp32 partial planes over K slices, then one
-# reduce pass with the fused epilogue -- gemm.hip nt_splitk_reduce_kernel) for
-# row GEMMs whose output tiles cannot fill 256 CUs over a deep K: the 1x1
-# convolutions of stages 3-4 at the reference's batch 32 (M = 1568, N = 512,
-# K = 2048 is 52 tiles of 128x128).
-_SPLITK_BASE = (4, 1, 1001, 1002, 1003)
-_SPLITK_MAX_OUT = 1 << 22
-_SPLITK_GRIDS = (0, 1 << 20)
-
-
-def _splitk_cfgs(dt: torch.dtype, M: int, N: int, K: int) -> List[int]:
-    """Split-K candidate configs of an [M, K] x [N, K]^T fp32 GEMM (empty when
-    its output alone fills the chip)."""
-    if dt != torch.float32 or M * N > _SPLITK_MAX_OUT:
-        return []
-    base = list(_SPLITK_BASE) + ([c + X6 for c in _SPLITK_BASE] if _x6() else [])
-    return [c + 10000 * S for S in (2, 4, 8) if K % (64 * S) == 0 and K // S >= 128 for c in base]
-
-
-# (the implicit-GEMM convolutions split the same way over their (tap, channel)
-# K slices: conv_nt with cfg + 10000 S)
-
-
-def _dkey(dt: torch.dtype) -> tuple:
-    """Autotune key suffix: fp32 keys are tagged, bf16 keys keep their
-    round-2 form so the shipped tuning cache stays valid."""
-    if dt == torch.float32:
-        return ("f32", "x6") if _x6() else ("f32",)
-    return ()
 _zeros: Dict[torch.device, torch.Tensor] = {}
 
 
@@ -177,106 +68,6 @@ def _zero(dev: torch.device) -> torch.Tensor:
     if z is None:
         z = _zeros[dev] = torch.zeros(256, dtype=torch.bfloat16, device=dev)
     return z
-
-
-def _time(fn: Callable[[], None], reps: int = 5) -> float:
-    fn()
-    a = torch.cuda.Event(enable_timing=True)
-    b = torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / reps
-
-
-def _pick(key: tuple, cands: List[Tuple[tuple, Callable[[], None]]]) -> tuple:
-    """Fastest candidate for ``key`` (timed once per process, then cached):
-    a 3-repetition screen of every candidate, then the best four re-timed
-    with 12 repetitions (one noisy sample must not decide)."""
-    got = _choices.get(key)
-    if got is not None:
-        return got
-    if len(cands) == 1:
-        _choices[key] = cands[0][0]
-        return cands[0][0]
-    if not _TUNE:
-        # untuned: the first candidate that runs (a lazy-operand tile may refuse its LDS budget)
-        for tag, fn in cands:
-            try:
-                fn()
-            except RuntimeError:
-                continue
-            _choices[key] = tag
-            return tag
-        raise RuntimeError("no candidate ran for %s" % (key,))
-    log = _timings.setdefault(key, [])
-    screened = []
-    for tag, fn in cands:
-        try:
-            t = _time(fn, reps=3)
-        except RuntimeError as e:
-            log.append((tag, "error: %s" % str(e).splitlines()[0][:200]))
-            continue
-        screened.append((t, tag, fn))
-    screened.sort(key=lambda e: e[0])
-    best, best_t = cands[-1][0], float("inf")
-    timed = []
-    for _, tag, fn in screened[:4]:
-        t = _time(fn, reps=12)
-        log.append((tag, round(t, 4)))
-        timed.append((t, tag))
-        if t < best_t:
-            best, best_t = tag, t
-    if best[0] not in _OWN and _GK_MARGIN > 0:
-        # keep the hand-written kernel unless the vendor library is clearly faster
-        own = [(t, tag) for t, tag in timed if tag[0] in _OWN]
-        if own and min(own)[0] <= best_t * (1.0 + _GK_MARGIN):
-            best = min(own)[1]
-            log.append((best, "kept: within GKSGD_GK_MARGIN of %s" % (best_t,)))
-    _choices[key] = best
-    return best
-
-
-def tuning_log() -> Dict[tuple, list]:
-    """Per key, every candidate's measured ms (or its error) from the search."""
-    return dict(_timings)
-
-
-def load_choices(path: str) -> int:
-    """Seed the autotune cache from a JSON file written by save_choices()."""
-    import json
-    try:
-        with open(path) as f:
-            rows = json.load(f)
-    except (OSError, ValueError):
-        return 0
-    for k, v in rows:
-        _choices.setdefault(tuple(k), tuple(v))
-    return len(rows)
-
-
-def save_choices(path: str) -> None:
-    import json
-    with open(path, "w") as f:
-        json.dump([[list(k), list(v)] for k, v in sorted(_choices.items(), key=str)], f, indent=0)
-
-
-_CACHE = os.environ.get("GKSGD_GEMM_CACHE", os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(
-    os.path.abspath(__file__)))), "tuning", "gemm_choices.json"))
-if _TUNE and _CACHE and os.path.exists(_CACHE) and os.environ.get("GKSGD_GEMM_RETUNE", "0") == "0":
-    load_choices(_CACHE)
-    # GKSGD_GEMM_RETUNE_ONLY=dgrad_bn,...: retune only the keys of these directions
-    _only = {d for d in os.environ.get("GKSGD_GEMM_RETUNE_ONLY", "").split(",") if d}
-    if _only:
-        for _k in [k for k in _choices if k and k[0] in _only]:
-            del _choices[_k]
-
-
-def tuned_choices() -> Dict[tuple, tuple]:
-    """(direction, geometry...) -> chosen (impl, cfg, grid/splits)."""
-    return dict(_choices)
 
 
 def supported(x: torch.Tensor, conv: nn.Conv2d) -> bool:
@@ -317,7 +108,7 @@ _WX6 = os.environ.get("GKSGD_WINO_X6", "0") == "1"
 
 
 def _wx6_ok(Ci: int, Co: int) -> bool:
-    return _WX6 and _x6() and Ci % 32 == 0 and Co % 32 == 0
+    return _WX6 and f32_matmul() == "bf16x6" and Ci % 32 == 0 and Co % 32 == 0
 
 
 def _wino_tag(Ci: int, Co: int) -> tuple:
@@ -387,14 +178,14 @@ def _fwd(x: torch.Tensor, w: torch.Tensor, s: int, stats_box=None, bias=None, wp
     if k == 1 and s == 1:
         X, Y, Wm = _rows(x), _rows(y), w.reshape(K, C)
         run = lambda c, mb: g.gemm_nt(X, Wm, Y, c, mb, st, bias)  # noqa: E731
-        split = _splitk_cfgs(dt, M, K, C)
+        split = autotune.splitk_cfgs(dt, M, K, C)
     else:
         z = _zero(x.device)
         run = lambda c, mb: g.conv_nt(x, w, y, z, s, p, c, mb, st, bias)  # noqa: E731
-        split = _splitk_cfgs(dt, M, K, k * k * C)
+        split = autotune.splitk_cfgs(dt, M, K, k * k * C)
     b16 = bias.to(dt) if bias is not None else None
-    cands = [(("hip", c, mb), (lambda c=c, mb=mb: run(c, mb))) for c in _nt_cfgs(dt) for mb in _NT_GRIDS]
-    cands += [(("hip", c, mb), (lambda c=c, mb=mb: run(c, mb))) for c in split for mb in _SPLITK_GRIDS]
+    cands = autotune.hip_cands(run, product(autotune.nt_cfgs(dt), autotune.NT_GRIDS))
+    cands += autotune.hip_cands(run, product(split, autotune.SPLITK_GRIDS))
     wino = bias is None and _wino_ok(dt, k, s, C, K) and _wino_shape_fits(N, H, W, C, K)
     if wino:
         cands += _wino_cands(x, w, y, False, st, wp=wp)
@@ -406,12 +197,12 @@ def _fwd(x: torch.Tensor, w: torch.Tensor, s: int, stats_box=None, bias=None, wp
             g.bn_stats_partials(out.contiguous(memory_format=_CL), ws)
         return out
     ws = None
-    if st is not None and (("fwd", N, C, H, W, K, k, s, True) + _dkey(dt)) not in _choices and \
+    if st is not None and autotune.choice(("fwd", N, C, H, W, K, k, s, True) + autotune.dkey(dt)) is None and \
             g.bn_supported(K, x.element_size()):
         ws = torch.empty(int(g.bn_workspace_floats(M, K, x.element_size())), dtype=torch.float32, device=x.device)
     cands.append((("miopen", 0, 0), miopen))
-    ch = _pick(("fwd", N, C, H, W, K, k, s, st is not None) + _dkey(dt) + (_wino_tag(C, K) if wino else ()),
-               _forced(cands))
+    ch = autotune.pick(("fwd", N, C, H, W, K, k, s, st is not None) + autotune.dkey(dt) +
+                       (_wino_tag(C, K) if wino else ()), _forced(cands))
     if ch[0] == "miopen":
         return F.conv2d(x, w, b16, stride=s, padding=p).contiguous(memory_format=_CL)
     if ch[0] in ("wino", "wx6"):
@@ -452,7 +243,7 @@ def _dgrad(dy: torch.Tensor, w: torch.Tensor, x_shape, s: int, lz=None, plink=No
         dx = xs
         z = _zero(dy.device)
         run = lambda c, mb: g.conv_dgrad_s2(dy, w, dx, z, c, mb, **kw)  # noqa: E731
-        cands = [(("hip", c, mb), (lambda c=c, mb=mb: run(c, mb))) for c in _nt_cfgs(dt) for mb in _NT_GRIDS]
+        cands = autotune.hip_cands(run, product(autotune.nt_cfgs(dt), autotune.NT_GRIDS))
     if s == 1:
         dx = xs
         if k == 1:
@@ -460,17 +251,17 @@ def _dgrad(dy: torch.Tensor, w: torch.Tensor, x_shape, s: int, lz=None, plink=No
             Wt = _lazy(lambda: weight_prep.transposed_1x1(w, wp))
             run = lambda c, mb: g.gemm_nt(DY, Wt(), DX, c, mb, **kw)  # noqa: E731
             if lz is None:
-                split = _splitk_cfgs(dt, N * H * W, C, K)
+                split = autotune.splitk_cfgs(dt, N * H * W, C, K)
         else:
             # dX = conv(dY, W') with W'[c][kh][kw][k] = W[k][KH-1-kh][KW-1-kw][c]
             wf = _lazy(lambda: weight_prep.flipped_3x3(w, wp))
             z = _zero(dy.device)
             run = lambda c, mb: g.conv_nt(dy, wf(), dx, z, 1, p, c, mb, **kw)  # noqa: E731
-        cands = [(("hip", c, mb), (lambda c=c, mb=mb: run(c, mb))) for c in _nt_cfgs(dt) for mb in _NT_GRIDS]
-        cands += [(("hip", c, mb), (lambda c=c, mb=mb: run(c, mb))) for c in split for mb in _SPLITK_GRIDS]
+        cands = autotune.hip_cands(run, product(autotune.nt_cfgs(dt), autotune.NT_GRIDS))
+        cands += autotune.hip_cands(run, product(split, autotune.SPLITK_GRIDS))
     if lz is not None:
         cands.append((("mat", 0, 0), lambda: _dgrad(plink.materialize(), w, x_shape, s, wp=wp)))
-        ch = _pick(("dgrad", N, C, H, W, K, k, s) + _dkey(dt) + ("lz",), cands)
+        ch = autotune.pick(("dgrad", N, C, H, W, K, k, s) + autotune.dkey(dt) + ("lz",), cands)
         if ch[0] == "mat":
             return _dgrad(plink.materialize(), w, x_shape, s, wp=wp)
         run(ch[1], ch[2])
@@ -479,7 +270,7 @@ def _dgrad(dy: torch.Tensor, w: torch.Tensor, x_shape, s: int, lz=None, plink=No
     if wino:
         cands += _wino_cands(dy, w, dx, True, wp=wp)
     cands.append((("miopen", 0, 0), miopen))
-    ch = _pick(_dgrad_key(N, C, H, W, K, k, s, dt), _forced(cands))
+    ch = autotune.pick(_dgrad_key(N, C, H, W, K, k, s, dt), _forced(cands))
     if ch[0] == "miopen":
         return miopen().contiguous(memory_format=_CL)
     if ch[0] in ("wino", "wx6"):
@@ -519,7 +310,7 @@ def _lazy(make):
 
 def _dgrad_key(N, C, H, W, K, k, s, dt) -> tuple:
     wino = _wino_ok(dt, k, s, K, C) and _wino_shape_fits(N, H, W, C, K)
-    return ("dgrad", N, C, H, W, K, k, s) + _dkey(dt) + (_wino_tag(K, C) if wino else ())
+    return ("dgrad", N, C, H, W, K, k, s) + autotune.dkey(dt) + (_wino_tag(K, C) if wino else ())
 
 
 def _dgrad_bn(dy: torch.Tensor, w: torch.Tensor, x_shape, s: int, link, lz=None, plink=None,
@@ -543,7 +334,7 @@ def _dgrad_bn(dy: torch.Tensor, w: torch.Tensor, x_shape, s: int, link, lz=None,
         H2 = _rows(h)
         D2 = _rows(dy2) if dy2 is not None else None
         run = lambda c, mb: g.gemm_nt(DY, Wt(), DZ, c, mb, st, None, H2, D2, mask, **kw)  # noqa: E731
-        split = _splitk_cfgs(dt, M, C, K) if lz is None else []
+        split = autotune.splitk_cfgs(dt, M, C, K) if lz is None else []
     else:
         split = []
         wf = _lazy(lambda: weight_prep.flipped_3x3(w, wp))
@@ -551,20 +342,20 @@ def _dgrad_bn(dy: torch.Tensor, w: torch.Tensor, x_shape, s: int, link, lz=None,
         run = lambda c, mb: g.conv_nt(dy, wf(), dz, z, 1, p, c, mb, st, None, h, dy2, mask, **kw)  # noqa: E731
     # 64x64-per-wave tiles (cfg digit 1-4) and the fp32 32x64 family (cfg >= 1000) carry the
     # BN-backward epilogue
-    cands = [(("hip", c, mb), (lambda c=c, mb=mb: run(c, mb))) for c in _nt_cfgs(dt) if c % 10 <= 4 or c >= 1000
-             for mb in _NT_GRIDS]
-    cands += [(("hip", c, mb), (lambda c=c, mb=mb: run(c, mb))) for c in split for mb in _SPLITK_GRIDS]
-    key = ("dgrad_bn", N, C, H, W, K, k, s, dy2 is not None) + _dkey(dt)
+    bn_cfgs = [c for c in autotune.nt_cfgs(dt) if c % 10 <= 4 or c >= 1000]
+    cands = autotune.hip_cands(run, product(bn_cfgs, autotune.NT_GRIDS))
+    cands += autotune.hip_cands(run, product(split, autotune.SPLITK_GRIDS))
+    key = ("dgrad_bn", N, C, H, W, K, k, s, dy2 is not None) + autotune.dkey(dt)
     if lz is not None:
         cands.append((("mat", 0, 0), lambda: _dgrad_bn(plink.materialize(), w, x_shape, s, link, wp=wp)))
-        ch = _pick(key + ("lz",), cands)
+        ch = autotune.pick(key + ("lz",), cands)
         if ch[0] == "mat":
             return _dgrad_bn(plink.materialize(), w, x_shape, s, link, wp=wp)
     else:
         if _wino_ok(dt, k, s, K, C) and _wino_shape_fits(N, H, W, C, K):
             cands += _wino_cands(dy, w, dz, True, st, (h, dy2, mask), wp=wp)
             key = key + _wino_tag(K, C)
-        ch = _pick(key, _forced(cands))
+        ch = autotune.pick(key, _forced(cands))
     if ch[0] in ("wino", "wx6"):
         rows = dict(cands)[ch]()
     else:
@@ -582,7 +373,7 @@ def _bn_fusable(link, s: int, dgrad_key: tuple) -> bool:
         return False
     if link.h.dtype != dgrad_key_dtype(dgrad_key):
         return False
-    ch = _choices.get(dgrad_key)
+    ch = autotune.choice(dgrad_key)
     return ch is None or ch[0] in ("hip", "wino", "wx6")
 
 
@@ -593,7 +384,7 @@ def dgrad_key_dtype(key: tuple) -> torch.dtype:
 def _wgrad_key(x: torch.Tensor, w: torch.Tensor, s: int, lz=None) -> tuple:
     N, C, H, W, K, k, p, OH, OW = _geom(x.shape, w, s)
     wino = lz is None and _wino_ok(x.dtype, k, s, C, K) and C % 64 == 0 and _wino_shape_fits(N, H, W, C, K)
-    return ("wgrad", N, C, H, W, K, k, s) + _dkey(x.dtype) + (("lz",) if lz is not None else ()) + \
+    return ("wgrad", N, C, H, W, K, k, s) + autotune.dkey(x.dtype) + (("lz",) if lz is not None else ()) + \
         (("wino",) if wino else ())
 
 
@@ -605,7 +396,7 @@ def _wgrad_into(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, s: int, out_
     g = _g()
     dt = x.dtype
     key = _wgrad_key(x, w, s, lz)
-    scratch = torch.zeros_like(out_f32) if key not in _choices else None
+    scratch = torch.zeros_like(out_f32) if autotune.choice(key) is None else None
     kw = _lz_kw(lz, rows=(k == 1 and s == 1)) if lz is not None else {}
 
     def miopen():
@@ -617,15 +408,12 @@ def _wgrad_into(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, s: int, out_
     else:
         z = _zero(x.device)
         run = lambda o, c, sp: g.conv_tn_acc(dy, x, o, z, s, p, c, sp, **kw)  # noqa: E731
-    tn = list(_tn_cfgs(dt))
-    if dt == torch.float32 and N * OH * OW <= _TN_SMALL_M:
-        tn += _TN_SMALL_F32   # small batches: more / fewer pixel splits than the two-rounds default
-        if _x6():
-            tn += [(c + X6, sp) for c, sp in _TN_SMALL_F32]
-    cands = [(("hip", c, sp), (lambda c=c, sp=sp: run(scratch, c, sp))) for c, sp in tn]
+    # small batches: more / fewer pixel splits than the two-rounds default
+    tn = autotune.tn_cfgs(dt) + autotune.tn_small_cfgs(dt, N * OH * OW)
+    cands = autotune.hip_cands(lambda c, sp: run(scratch, c, sp), tn)
     if lz is not None:
         cands.append((("mat", 0, 0), lambda: _wgrad_into(plink.materialize(), x, w, s, scratch)))
-        ch = _pick(key, cands)
+        ch = autotune.pick(key, cands)
         if ch[0] == "mat":
             _wgrad_into(plink.materialize(), x, w, s, out_f32)
         else:
@@ -652,7 +440,7 @@ def _wgrad_into(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, s: int, out_
         from . import accum_grad_
         accum_grad_(o, miopen().contiguous(memory_format=_CL))
     cands.append((("miopen", 0, 0), lambda: miopen_acc(scratch)))
-    ch = _pick(key, _forced(cands))
+    ch = autotune.pick(key, _forced(cands))
     if ch[0] == "miopen":
         miopen_acc(out_f32)
         return
@@ -727,7 +515,7 @@ class _FastConvFn(torch.autograd.Function):
             sink.grad_view.is_contiguous(memory_format=_CL)
         fork = direct and lz is None and not getattr(sink, "shared", False) and \
             streams.worth(x.device, 2.0 * dy.numel() * x.shape[1] * w.shape[2] * w.shape[3]) and \
-            _choices.get(_wgrad_key(x, w, s), ("",))[0] in _FORKABLE
+            (autotune.choice(_wgrad_key(x, w, s)) or ("",))[0] in _FORKABLE
 
         # the bias gradient (a column pass over dy into its arena view) rides along
         bs0 = ctx.bias_sink if ctx.has_bias and ctx.needs_input_grad[6] else None

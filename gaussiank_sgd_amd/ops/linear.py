@@ -5,7 +5,7 @@ HIP column pass (``csrc/kernels/linear.hip``) that adds straight into the
 optimizer's fp32 gradient arena.
 
 A linear layer over the M = prod(x.shape[:-1]) rows is the GEMM of a 1x1
-convolution over NHWC pixel rows (ops/conv1x1.py):
+convolution over NHWC pixel rows (ops/conv1x1.py), tuned by ops/autotune.py:
 
   forward      y[M, N]  = x[M, K] . W[N, K]^T (+ b in the epilogue)   gemm_nt
   grad-input   dx[M, K] = dy[M, N] . Wt[K, N]^T                       gemm_nt (Wt = W^T)
@@ -30,6 +30,7 @@ models/lstm.py:29); BERT is not in the reference (BASELINE config 5).
 from __future__ import annotations
 
 import os
+from itertools import product
 from typing import Optional
 
 import torch
@@ -37,7 +38,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import accum_grad_, load, require_native
-from . import conv1x1 as _cv
+from . import autotune
 from . import streams
 
 _ENABLED = os.environ.get("GKSGD_FASTLINEAR", "1") != "0"
@@ -118,6 +119,13 @@ def _pad_ok(t: torch.Tensor) -> bool:
     return _PAD and t.is_cuda
 
 
+def _is_blas(key: tuple) -> bool:
+    """Is ``key`` tuned and its choice hipBLASLt?  (Then the call skips what
+    only the HIP candidates need.)"""
+    ch = autotune.choice(key)
+    return ch is not None and ch[0] == "blas"
+
+
 def _fwd(x2: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor],
          b16: Optional[torch.Tensor] = None) -> torch.Tensor:
     """y = x2 . w^T (+ bias) in x2's dtype (bf16, or fp32: the fp32 MFMA
@@ -137,10 +145,10 @@ def _fwd(x2: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor],
         return _fwd_padded(x2, w, bias, blas)
     g = _g()
     y = torch.empty(M, N, dtype=dt, device=x2.device)
-    cands = [(("hip", c, mb), (lambda c=c, mb=mb: g.gemm_nt(x2, w, y, c, mb, None, bias)))
-             for c in _cv._nt_cfgs(dt) for mb in _cv._NT_GRIDS]
+    cands = autotune.hip_cands(lambda c, mb: g.gemm_nt(x2, w, y, c, mb, None, bias),
+                               product(autotune.nt_cfgs(dt), autotune.NT_GRIDS))
     cands.append((("blas", 0, 0), blas))
-    ch = _cv._pick(("lin_fwd", M, K, N, bias is not None) + _cv._dkey(dt), cands)
+    ch = autotune.pick(("lin_fwd", M, K, N, bias is not None) + autotune.dkey(dt), cands)
     if ch[0] == "blas":
         return blas()
     g.gemm_nt(x2, w, y, ch[1], ch[2], None, bias)
@@ -163,13 +171,12 @@ def _fwd_padded(x2: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor],
         yp = torch.empty(M, Np, dtype=dt, device=x2.device)
         g.gemm_nt(xp, wp, yp, c, mb, None, bp)
         return yp[:, :N]
-    key = ("lin_fwd", M, K, N, bias is not None) + _cv._dkey(dt) + ("pad",)
-    got = _cv._choices.get(key)
-    if got is not None and got[0] == "blas":
+    key = ("lin_fwd", M, K, N, bias is not None) + autotune.dkey(dt) + ("pad",)
+    if _is_blas(key):
         return blas()
-    cands = [(("hip", c, mb), (lambda c=c, mb=mb: padded(c, mb))) for c in _cv._nt_cfgs(dt) for mb in _cv._NT_GRIDS]
+    cands = autotune.hip_cands(padded, product(autotune.nt_cfgs(dt), autotune.NT_GRIDS))
     cands.append((("blas", 0, 0), blas))
-    ch = _cv._pick(key, cands)
+    ch = autotune.pick(key, cands)
     if ch[0] == "blas":
         return blas()
     return padded(ch[1], ch[2])
@@ -182,9 +189,8 @@ def _dgrad_padded(dy2: torch.Tensor, w: torch.Tensor, pads: Optional[dict] = Non
     Kp, Np = _p64(K), _p64(N)
     dt = dy2.dtype
     g = _g()
-    key = ("lin_dgrad", M, K, N) + _cv._dkey(dt) + ("pad",)
-    got = _cv._choices.get(key)
-    if got is not None and got[0] == "blas":
+    key = ("lin_dgrad", M, K, N) + autotune.dkey(dt) + ("pad",)
+    if _is_blas(key):
         return torch.mm(dy2, w)
 
     def padded(c, mb, cache=None):
@@ -193,9 +199,9 @@ def _dgrad_padded(dy2: torch.Tensor, w: torch.Tensor, pads: Optional[dict] = Non
         dxp = torch.empty(M, Kp, dtype=dt, device=dy2.device)
         g.gemm_nt(dyp, wtp, dxp, c, mb)
         return dxp[:, :K]
-    cands = [(("hip", c, mb), (lambda c=c, mb=mb: padded(c, mb))) for c in _cv._nt_cfgs(dt) for mb in _cv._NT_GRIDS]
+    cands = autotune.hip_cands(padded, product(autotune.nt_cfgs(dt), autotune.NT_GRIDS))
     cands.append((("blas", 0, 0), lambda: torch.mm(dy2, w)))
-    ch = _cv._pick(key, cands)
+    ch = autotune.pick(key, cands)
     if ch[0] == "blas":
         return torch.mm(dy2, w)
     return padded(ch[1], ch[2], pads)
@@ -206,19 +212,18 @@ def _dgrad(dy2: torch.Tensor, w: torch.Tensor, pads: Optional[dict] = None) -> t
     M, N = dy2.shape
     K = w.shape[1]
     dt = dy2.dtype
-    key = ("lin_dgrad", M, K, N) + _cv._dkey(dt)
-    got = _cv._choices.get(key)
+    key = ("lin_dgrad", M, K, N) + autotune.dkey(dt)
     if not _hip_gemm_ok(K, N) and _pad_ok(dy2):
         return _dgrad_padded(dy2, w, pads)
-    if not _hip_gemm_ok(K, N) or (got is not None and got[0] == "blas"):
+    if not _hip_gemm_ok(K, N) or _is_blas(key):
         return torch.mm(dy2, w)
     g = _g()
     dx = torch.empty(M, K, dtype=dt, device=dy2.device)
     wt = w.t().contiguous()
-    cands = [(("hip", c, mb), (lambda c=c, mb=mb: g.gemm_nt(dy2, wt, dx, c, mb)))
-             for c in _cv._nt_cfgs(dt) for mb in _cv._NT_GRIDS]
+    cands = autotune.hip_cands(lambda c, mb: g.gemm_nt(dy2, wt, dx, c, mb),
+                               product(autotune.nt_cfgs(dt), autotune.NT_GRIDS))
     cands.append((("blas", 0, 0), lambda: torch.mm(dy2, w)))
-    ch = _cv._pick(key, cands)
+    ch = autotune.pick(key, cands)
     if ch[0] == "blas":
         return torch.mm(dy2, w)
     g.gemm_nt(dy2, wt, dx, ch[1], ch[2])
@@ -244,13 +249,13 @@ def _wgrad_into(dy2: torch.Tensor, x2: torch.Tensor, out: torch.Tensor, pads: Op
         blas(out)
         return
     g = _g()
-    key = ("lin_wgrad", M, K, N) + _cv._dkey(dy2.dtype)
-    scratch = torch.zeros_like(out) if key not in _cv._choices else None
+    key = ("lin_wgrad", M, K, N) + autotune.dkey(dy2.dtype)
+    scratch = torch.zeros_like(out) if autotune.choice(key) is None else None
     cands = []
     padded = None
+    tn = autotune.tn_cfgs(torch.float32 if f32 else torch.bfloat16)
     if _hip_gemm_ok(K, N):
-        cands = [(("hip", c, sp), (lambda c=c, sp=sp: g.gemm_tn_acc(dy2, x2, scratch, c, sp)))
-                 for c, sp in _cv._tn_cfgs(torch.float32 if f32 else torch.bfloat16)]
+        cands = autotune.hip_cands(lambda c, sp: g.gemm_tn_acc(dy2, x2, scratch, c, sp), tn)
     elif _pad_ok(dy2):
         # zero-padded operands into a padded fp32 scratch, then one add of its
         # [:N, :K] block into the target (see _fwd_padded)
@@ -263,12 +268,11 @@ def _wgrad_into(dy2: torch.Tensor, x2: torch.Tensor, out: torch.Tensor, pads: Op
             op = torch.zeros(Np, Kp, dtype=torch.float32, device=dy2.device)
             g.gemm_tn_acc(dyp, xp, op, c, sp)
             o.add_(op[:N, :K])
-        scratch = torch.zeros_like(out) if key not in _cv._choices else None
-        cands = [(("hip", c, sp), (lambda c=c, sp=sp: padded(scratch, c, sp)))
-                 for c, sp in _cv._tn_cfgs(torch.float32 if f32 else torch.bfloat16)]
+        scratch = torch.zeros_like(out) if autotune.choice(key) is None else None
+        cands = autotune.hip_cands(lambda c, sp: padded(scratch, c, sp), tn)
     cands.append((("blas32", 0, 0), lambda: blas32(scratch)))
     cands.append((("blas", 0, 0), lambda: blas(scratch)))
-    ch = _cv._pick(key, cands)
+    ch = autotune.pick(key, cands)
     if ch[0] == "blas":
         blas(out)
     elif ch[0] == "blas32":
@@ -287,10 +291,10 @@ def _wgrad_forkable(dy2: torch.Tensor, x2: torch.Tensor) -> bool:
     K = x2.shape[1]
     if not streams.worth(dy2.device, 2.0 * M * N * K):
         return False
-    key = ("lin_wgrad", M, K, N) + _cv._dkey(dy2.dtype)
+    key = ("lin_wgrad", M, K, N) + autotune.dkey(dy2.dtype)
     if not _hip_gemm_ok(K, N):
         key = key + ("pad",)
-    ch = _cv._choices.get(key)
+    ch = autotune.choice(key)
     return ch is not None and ch[0] == "hip"
 
 

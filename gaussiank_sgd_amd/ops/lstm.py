@@ -40,7 +40,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import load, require_native
+from . import autotune, load, require_native
 from .linear import _dgrad as _lin_dgrad
 from .linear import _fwd as _lin_fwd
 from .linear import _target, _wgrad_forkable, _wgrad_into, bias_grad_acc_
@@ -87,7 +87,7 @@ def _cdiv(a: int, b: int) -> int:
 
 # Step GEMM per direction: None = autotuned once per (direction, dtype, batch,
 # H) among hipBLASLt and the split-K kernel at every K-slice count S (cached
-# with the other GEMM choices, ops/conv1x1.py _pick).  An int forces the
+# with the other GEMM choices, ops/autotune.py pick).  An int forces the
 # round-5 rule instead: split-K with the default S up to that batch, hipBLASLt
 # above.  Measured on MI355X (bench/lstm_x6_probe.py, profiles/r06_lstm_step_probe.json),
 # fp32 H = 1500: B = 20 forward split-K S = 8 11.9 us vs the rule's S = 4 18.5,
@@ -124,9 +124,8 @@ def _step_plan(direction: str, cd: torch.dtype, B: int, H: int, dev) -> Tuple[st
         if B > mx:
             return ("blas", 0)
         return ("hip", _splits(kb, nb * mb, target=512 if fwd else 256))
-    from . import conv1x1 as _cv
     key = ("lstm_step", direction, B, H, "f32" if cd == torch.float32 else "bf16")
-    got = _cv._choices.get(key)
+    got = autotune.choice(key)
     if got is not None:
         return (got[0], int(got[1]))
     g = _g()
@@ -142,7 +141,7 @@ def _step_plan(direction: str, cd: torch.dtype, B: int, H: int, dev) -> Tuple[st
     ab = torch.zeros(B, H if fwd else 4 * H, dtype=cd, device=dev)
     wb = torch.zeros(4 * H, H, dtype=cd, device=dev)
     cands.append((("blas", 0, 0), (lambda: torch.mm(ab, wb.t())) if fwd else (lambda: torch.mm(ab, wb))))
-    ch = _cv._pick(key, cands)
+    ch = autotune.pick(key, cands)
     return (ch[0], int(ch[1]))
 
 

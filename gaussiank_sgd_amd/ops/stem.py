@@ -27,17 +27,14 @@ import os
 import torch
 import torch.nn as nn
 
-from . import load
+from . import autotune, load
 
 _CL = torch.channels_last
 _ENABLED = os.environ.get("GKSGD_STEM", "1") != "0"
 _F32 = os.environ.get("GKSGD_STEM_F32", "1") != "0"   # fp32 stem kernels (else MIOpen at fp32)
 # fp32 stem forward on the bf16x6 kernel when the fp32 GEMM family is bf16x6
-# (ops/conv1x1.py set_f32_matmul; GKSGD_STEM_X6=0 keeps the fp32-MFMA kernel)
+# (ops/autotune.py set_f32_matmul; GKSGD_STEM_X6=0 keeps the fp32-MFMA kernel)
 _X6 = os.environ.get("GKSGD_STEM_X6", "1") != "0"
-
-
-from . import conv1x1 as _cv  # noqa: E402
 
 
 def _g():
@@ -100,7 +97,7 @@ class _StemF32Fn(torch.autograd.Function):
         st = None
         if stats_box is not None:
             st = torch.empty(2, 512, 64, dtype=torch.float32, device=x.device)
-        x6 = _X6 and _cv.f32_matmul() == "bf16x6"
+        x6 = _X6 and autotune.f32_matmul() == "bf16x6"
         if x6:
             # bf16x6 products (fp32-accurate, stem_f32.hip stem_f32x6_fwd_kernel):
             # the weight planes are split into a per-call workspace

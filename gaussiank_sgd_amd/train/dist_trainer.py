@@ -48,8 +48,8 @@ def ssgd(dnn, dataset, data_dir, nworkers, lr, batch_size, nsteps_update, max_ep
         torch.cuda.set_device(hvd.local_rank() % torch.cuda.device_count())
         device = "cuda"
     if f32_matmul is not None:
-        from ..ops import conv1x1
-        conv1x1.set_f32_matmul(f32_matmul)
+        from ..ops import autotune
+        autotune.set_f32_matmul(f32_matmul)
     # Resume: rank 0 loads the model, momentum and its own compressor state
     # (reference dist_trainer.py:26-27 loads on rank 0 only); every other rank
     # reads ITS OWN per-rank file for its residuals / DGC velocities -- those
@@ -280,7 +280,7 @@ def build_parser():
                    choices=["native", "bf16x6"],
                    help="fp32 convolution / linear GEMM algorithm (default: %(default)s, the same as bench.py and "
                         "the library): native = fp32 MFMA only; bf16x6 = the tuner may also pick the "
-                        "fp32-accurate bf16x6 product kernels (ops/conv1x1.py set_f32_matmul)")
+                        "fp32-accurate bf16x6 product kernels (ops/autotune.py set_f32_matmul)")
     p.add_argument("--train-samples", type=int, default=None,
                    help="synthetic epoch length in samples (default: the dataset's real size)")
     p.add_argument("--checkpoint-every", type=int, default=2,

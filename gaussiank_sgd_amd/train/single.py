@@ -40,8 +40,8 @@ def train_with_single(dnn, dataset, data_dir, nworkers, lr, batch_size, nsteps_u
         torch.cuda.set_device(0)
         device = "cuda"
     if f32_matmul is not None:
-        from ..ops import conv1x1
-        conv1x1.set_f32_matmul(f32_matmul)
+        from ..ops import autotune
+        autotune.set_f32_matmul(f32_matmul)
     trainer = DLTrainer(0, nworkers, dist=False, batch_size=batch_size, is_weak_scaling=True, ngpus=1,
                         data_dir=data_dir, dataset=dataset, dnn=dnn, lr=lr, nworkers=nworkers, prefix="singlegpu",
                         num_steps=num_steps, device=device, amp=amp, channels_last=channels_last,

@@ -8,7 +8,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 
 def main():
     import torch
-    from gaussiank_sgd_amd.ops import conv1x1
+    from gaussiank_sgd_amd.ops import autotune, conv1x1
     from gaussiank_sgd_amd.ops import weight_prep as wpm
     from gaussiank_sgd_amd.train import DLTrainer
     bs = int(sys.argv[1]) if len(sys.argv) > 1 else 4
@@ -34,7 +34,7 @@ def main():
             kinds[k[0]] = kinds.get(k[0], 0) + 1
         print("step", i, "fwd calls", calls, "entries", kinds, "launches", t.weight_prep.launches, flush=True)
     ch = {}
-    for k, v in conv1x1.tuned_choices().items():
+    for k, v in autotune.tuned_choices().items():
         ch[(k[0], v[0])] = ch.get((k[0], v[0]), 0) + 1
     print("choices", ch, flush=True)
 

@@ -99,9 +99,9 @@ def test_resnet50_bn_link_matches_unfused(monkeypatch):
     the comparison is relative to the unfused bf16 path, not absolute), and
     the fused grad-input must actually run for every linked BN."""
     from gaussiank_sgd_amd.models import resnet50
-    from gaussiank_sgd_amd.ops import conv1x1
-    monkeypatch.setattr(conv1x1, "_TUNE", False)
-    monkeypatch.setattr(conv1x1, "_choices", {})
+    from gaussiank_sgd_amd.ops import autotune, conv1x1
+    monkeypatch.setattr(autotune, "_TUNE", False)
+    monkeypatch.setattr(autotune, "_choices", {})
     calls = []
     orig = conv1x1._dgrad_bn
 

@@ -107,9 +107,9 @@ def test_conv1x1_shadow_arena_grad():
 @pytest.fixture
 def hip_only(monkeypatch):
     """Force the HIP kernels (no autotune against MIOpen) for one test."""
-    from gaussiank_sgd_amd.ops import conv1x1
-    monkeypatch.setattr(conv1x1, "_TUNE", False)
-    monkeypatch.setattr(conv1x1, "_choices", {})
+    from gaussiank_sgd_amd.ops import autotune
+    monkeypatch.setattr(autotune, "_TUNE", False)
+    monkeypatch.setattr(autotune, "_choices", {})
 
 
 @pytest.mark.parametrize("k,s,C,K", [(1, 1, 64, 256), (3, 1, 64, 64), (3, 2, 128, 128), (1, 2, 256, 512)])

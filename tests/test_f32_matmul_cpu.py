@@ -1,4 +1,4 @@
-"""fp32 matmul algorithm selection (ops/conv1x1.py set_f32_matmul) on the CPU:
+"""fp32 matmul algorithm selection (ops/autotune.py set_f32_matmul) on the CPU:
 the bf16x6 candidates are offered only in "bf16x6" mode and only for fp32
 operands, their cfgs carry the 100000 digit (gemm_cfg.h product
 family), split-K keeps both digits, autotune keys are tagged so the two
@@ -16,46 +16,47 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+from gaussiank_sgd_amd.ops import autotune as at  # noqa: E402
 from gaussiank_sgd_amd.ops import conv1x1 as cv  # noqa: E402
 
 
 @pytest.fixture
 def mode():
-    prev = cv.f32_matmul()
+    prev = at.f32_matmul()
     yield
-    cv.set_f32_matmul(prev)
+    at.set_f32_matmul(prev)
 
 
 def test_modes_and_candidates(mode):
-    cv.set_f32_matmul("native")
-    nat = cv._nt_cfgs(torch.float32)
-    assert all(c < cv.X6 for c in nat)
-    assert cv._dkey(torch.float32) == ("f32",)
-    assert all(c < cv.X6 for c, _ in cv._tn_cfgs(torch.float32))
-    prev = cv.set_f32_matmul("bf16x6")
-    assert prev == "native" and cv.f32_matmul() == "bf16x6"
-    x6 = cv._nt_cfgs(torch.float32)
+    at.set_f32_matmul("native")
+    nat = at.nt_cfgs(torch.float32)
+    assert all(c < at.X6 for c in nat)
+    assert at.dkey(torch.float32) == ("f32",)
+    assert all(c < at.X6 for c, _ in at.tn_cfgs(torch.float32))
+    prev = at.set_f32_matmul("bf16x6")
+    assert prev == "native" and at.f32_matmul() == "bf16x6"
+    x6 = at.nt_cfgs(torch.float32)
     assert set(nat) < set(x6)
-    extra = [c for c in x6 if c >= cv.X6]
-    assert extra and all(c // cv.X6 in (1, 2, 3) and (c % cv.X6) // 10000 == 0 for c in extra)
-    assert cv._dkey(torch.float32) == ("f32", "x6")
-    assert any(c >= cv.X6 for c, _ in cv._tn_cfgs(torch.float32))
+    extra = [c for c in x6 if c >= at.X6]
+    assert extra and all(c // at.X6 in (1, 2, 3) and (c % at.X6) // 10000 == 0 for c in extra)
+    assert at.dkey(torch.float32) == ("f32", "x6")
+    assert any(c >= at.X6 for c, _ in at.tn_cfgs(torch.float32))
     # bf16 operands are untouched by the fp32 algorithm choice
-    assert cv._nt_cfgs(torch.bfloat16) == cv._NT_CFGS and cv._dkey(torch.bfloat16) == ()
-    assert cv._tn_cfgs(torch.bfloat16) == cv._TN_CFGS
+    assert at.nt_cfgs(torch.bfloat16) == at._NT_CFGS and at.dkey(torch.bfloat16) == ()
+    assert at.tn_cfgs(torch.bfloat16) == at._TN_CFGS
     # split-K: S in the 10000 digit, the bf16x6 flag in the 100000 digit
-    sk = cv._splitk_cfgs(torch.float32, 1568, 512, 2048)
-    assert any(c >= cv.X6 for c in sk)
+    sk = at.splitk_cfgs(torch.float32, 1568, 512, 2048)
+    assert any(c >= at.X6 for c in sk)
     for c in sk:
         assert (c // 10000) % 10 in (2, 4, 8)
     with pytest.raises(ValueError):
-        cv.set_f32_matmul("tf32")
+        at.set_f32_matmul("tf32")
 
 
 def test_keys_do_not_collide(mode):
-    cv.set_f32_matmul("native")
+    at.set_f32_matmul("native")
     k1 = cv._dgrad_key(512, 256, 14, 14, 1024, 1, 1, torch.float32)
-    cv.set_f32_matmul("bf16x6")
+    at.set_f32_matmul("bf16x6")
     k2 = cv._dgrad_key(512, 256, 14, 14, 1024, 1, 1, torch.float32)
     assert k1 != k2 and k2[:len(k1)] == k1
     assert cv.dgrad_key_dtype(k2) == torch.float32

@@ -365,30 +365,30 @@ def test_splitk_candidates_only_for_underfilled_deep_gemms():
     is small (<= 4 M elements) and K splits into >= 128-deep, 64-aligned
     planes; bf16 never gets them (partial planes are fp32)."""
     import torch
-    from gaussiank_sgd_amd.ops import conv1x1 as cv
+    from gaussiank_sgd_amd.ops import autotune as cv
     prev = cv.set_f32_matmul("native")     # the S digit alone (bf16x6 adds the 100000 digit)
     try:
         _splitk_checks(cv, torch)
         cv.set_f32_matmul("bf16x6")
-        x6 = cv._splitk_cfgs(torch.float32, 1568, 512, 2048)
+        x6 = cv.splitk_cfgs(torch.float32, 1568, 512, 2048)
         assert {(x % cv.X6) // 10000 for x in x6} == {2, 4, 8} and any(x >= cv.X6 for x in x6)
     finally:
         cv.set_f32_matmul(prev)
 
 
 def _splitk_checks(cv, torch):
-    c = cv._splitk_cfgs(torch.float32, 1568, 512, 2048)          # stage-4 1x1 at bs32
+    c = cv.splitk_cfgs(torch.float32, 1568, 512, 2048)          # stage-4 1x1 at bs32
     assert c and all(x >= 20000 for x in c)
     S = sorted({x // 10000 for x in c})
     assert S == [2, 4, 8]
     assert all(2048 % (64 * s) == 0 and 2048 // s >= 128 for s in S)
     assert {x % 10000 for x in c} == set(cv._SPLITK_BASE)
-    assert cv._splitk_cfgs(torch.bfloat16, 1568, 512, 2048) == []
-    assert cv._splitk_cfgs(torch.float32, 25088 * 16, 512, 2048) == []   # bs512: the output fills the chip
-    assert {x // 10000 for x in cv._splitk_cfgs(torch.float32, 1568, 512, 256)} == {2}   # 256 / 4 < 128
-    assert cv._splitk_cfgs(torch.float32, 1568, 512, 192) == []           # 192 % 128 != 0
+    assert cv.splitk_cfgs(torch.bfloat16, 1568, 512, 2048) == []
+    assert cv.splitk_cfgs(torch.float32, 25088 * 16, 512, 2048) == []   # bs512: the output fills the chip
+    assert {x // 10000 for x in cv.splitk_cfgs(torch.float32, 1568, 512, 256)} == {2}   # 256 / 4 < 128
+    assert cv.splitk_cfgs(torch.float32, 1568, 512, 192) == []           # 192 % 128 != 0
     # implicit-GEMM convolutions split over their tap x channel depth (3x3 x 512)
-    assert {x // 10000 for x in cv._splitk_cfgs(torch.float32, 1568, 512, 9 * 512)} == {2, 4, 8}
+    assert {x // 10000 for x in cv.splitk_cfgs(torch.float32, 1568, 512, 9 * 512)} == {2, 4, 8}
 
 
 def test_winograd_split_candidates_small_grids_only():

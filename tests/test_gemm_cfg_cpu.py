@@ -32,7 +32,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from gaussiank_sgd_amd.ops import conv1x1 as cv  # noqa: E402
+from gaussiank_sgd_amd.ops import autotune as cv  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CXX = shutil.which(os.environ.get("CXX", "g++")) or shutil.which("c++") or shutil.which("clang++")

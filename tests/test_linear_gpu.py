@@ -22,9 +22,9 @@ def _gpu():
 @pytest.fixture
 def hip_only(monkeypatch):
     """Force the HIP GEMM kernels (no autotune against hipBLASLt) for one test."""
-    from gaussiank_sgd_amd.ops import conv1x1
-    monkeypatch.setattr(conv1x1, "_TUNE", False)
-    monkeypatch.setattr(conv1x1, "_choices", {})
+    from gaussiank_sgd_amd.ops import autotune
+    monkeypatch.setattr(autotune, "_TUNE", False)
+    monkeypatch.setattr(autotune, "_choices", {})
 
 
 @pytest.mark.parametrize("M,N", [(1000, 264), (37, 8), (4096, 768), (257, 3072), (4480, 10000)])
@@ -261,7 +261,7 @@ def test_fp32_linear_padded_operands_vs_fp64(hip_only, M, K, N, bias):
     """fp32 FastLinear with K / N not multiples of 64 (the LSTM's 1500-unit
     layers and 10k softmax): the HIP kernels on zero-padded operand copies
     (forward, grad-input, grad-weight into a padded scratch) against fp64."""
-    from gaussiank_sgd_amd.ops import conv1x1
+    from gaussiank_sgd_amd.ops import autotune
     from gaussiank_sgd_amd.ops.linear import FastLinear
     torch.manual_seed(M + K + N)
     m = FastLinear(K, N, bias=bias).cuda()
@@ -269,11 +269,11 @@ def test_fp32_linear_padded_operands_vs_fp64(hip_only, M, K, N, bias):
     y = m(x)
     assert y.shape == (M, N)
     # the padded HIP path ran (its tuner keys carry "pad")
-    assert any(k[0] == "lin_fwd" and k[-1] == "pad" for k in conv1x1._choices)
+    assert any(k[0] == "lin_fwd" and k[-1] == "pad" for k in autotune.tuned_choices())
     gy = torch.randn(M, N, device="cuda")
     (y * gy).sum().backward()
-    assert any(k[0] == "lin_dgrad" and k[-1] == "pad" for k in conv1x1._choices)
-    assert any(k[0] == "lin_wgrad" and k[-1] == "pad" for k in conv1x1._choices)
+    assert any(k[0] == "lin_dgrad" and k[-1] == "pad" for k in autotune.tuned_choices())
+    assert any(k[0] == "lin_wgrad" and k[-1] == "pad" for k in autotune.tuned_choices())
     xd = x.detach().double().requires_grad_(True)
     wd = m.weight.detach().double().requires_grad_(True)
     bd = m.bias.detach().double().requires_grad_(True) if bias else None

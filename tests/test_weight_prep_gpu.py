@@ -87,9 +87,9 @@ def test_resnet50_step_same_with_and_without_batching(monkeypatch, force):
     families are forced (fresh autotuner table) so the re-layouts the test
     needs are the ones registered: "hip" -> 1x1 transposes + 3x3 flips,
     "wino" -> Winograd filter transforms."""
-    from gaussiank_sgd_amd.ops import conv1x1
+    from gaussiank_sgd_amd.ops import autotune, conv1x1
     from gaussiank_sgd_amd.train import DLTrainer
-    monkeypatch.setattr(conv1x1, "_choices", {})
+    monkeypatch.setattr(autotune, "_choices", {})
     monkeypatch.setattr(conv1x1, "_FORCE", force)
 
     def run(enabled):

@@ -118,9 +118,9 @@ def test_wino_dgrad_bn_epilogue(g, twin, H):
 def test_fastconv2d_f32_winograd_autograd(monkeypatch):
     """FastConv2d fp32 3x3 stride-1 with the Winograd candidates forced:
     forward and grad-input run wino_conv and match fp64 torch."""
-    from gaussiank_sgd_amd.ops import conv1x1
+    from gaussiank_sgd_amd.ops import autotune, conv1x1
     monkeypatch.setattr(conv1x1, "_FORCE", "wino")
-    monkeypatch.setattr(conv1x1, "_choices", {})
+    monkeypatch.setattr(autotune, "_choices", {})
     torch.manual_seed(7)
     conv = conv1x1.FastConv2d(64, 128, 3, stride=1, padding=1, bias=False).cuda().to(memory_format=CL)
     x = torch.randn(4, 64, 14, 14, device="cuda").contiguous(memory_format=CL).requires_grad_(True)
