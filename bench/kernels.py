@@ -256,7 +256,60 @@ def main() -> int:
     topt = torch.optim.AdamW(ps, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, foreach=True)
     t = timeit(topt.step)
     report("torch AdamW foreach (context)", t, 7 * 4 * n, "161 tensors, host-side step count")
-    del topt, ps, wa, ga, ma, va
+    del topt, ps
+    # LAMB on the same arenas, the chunk table of the 161 tensors above (one trust ratio each): the two
+    # streaming passes apart (the binding's `passes` mask), then the whole step.  Expected from traffic
+    # alone: 6 + 5 = 11 arena passes against fused_adam's 7, about 1.6x its time.
+    ltab = ops.make_chunk_table([(a, b - a, 0, i) for i, (a, b) in enumerate(cuts)], dev)
+    lws = ops.make_lamb_workspace(ltab, dev)
+    hpl = dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, adapt=True, trust_clip=None)
+
+    def lamb_passes(mask, zero_grad, shadow):
+        ops._ops().fused_lamb(wa, ma, va, ga, ltab, stp, lws.seg_range, lws.part, lws.trust, [hpl["lr"]],
+                              [hpl["betas"][0]], [hpl["betas"][1]], [hpl["eps"]], [hpl["weight_decay"]], [1], [0.0],
+                              zero_grad, None, shadow, None, mask)
+    ga.normal_()
+    t = timeit(lambda: lamb_passes(1, False, None))
+    report("lamb_moments (r w,g,m,v; w m,v)", t, 6 * 4 * n, "incl. the step tick; per-chunk norm partials")
+    t = timeit(lambda: lamb_passes(2, False, None))
+    report("lamb_trust (161 tensors)", t, 16 * (ltab.numel() // 2), "one wave per tensor")
+    t = timeit(lambda: lamb_passes(4, False, None))
+    report("lamb_apply (r w,m,v; w w)", t, 4 * 4 * n)
+    t = timeit(lambda: lamb_passes(4, True, sh))
+    report("lamb_apply + zero g + bf16 shadow", t, 5 * 4 * n + 2 * n)
+    t = timeit(lambda: ops.fused_lamb_(wa, ma, va, ga, ltab, [hpl], stp, lws, zero_grad=False))
+    report("fused_lamb whole step", t, 10 * 4 * n, "tick + 3 launches")
+    t = timeit(lambda: ops.fused_lamb_(wa, ma, va, ga, ltab, [hpl], stp, lws, zero_grad=True, w_bf16=sh))
+    report("fused_lamb + zero g + bf16 shadow", t, 11 * 4 * n + 2 * n, "11 arena passes; fused_adam: 7 + shadow")
+    # context: the same formula with torch._foreach_* over the 161 tensors (what a user would run
+    # otherwise): no host sync, neither zeroes g nor writes the shadow
+    ga.normal_()
+    fw = [wa[a:b] for a, b in cuts]
+    fg = [ga[a:b] for a, b in cuts]
+    fm = [ma[a:b] for a, b in cuts]
+    fv = [va[a:b] for a, b in cuts]
+    fstep = [0]
+
+    def foreach_lamb():
+        fstep[0] += 1
+        b1, b2 = hpl["betas"]
+        bc1, bc2 = 1.0 - b1 ** fstep[0], 1.0 - b2 ** fstep[0]
+        torch._foreach_lerp_(fm, fg, 1.0 - b1)
+        torch._foreach_mul_(fv, b2)
+        torch._foreach_addcmul_(fv, fg, fg, value=1.0 - b2)
+        den = torch._foreach_sqrt(fv)
+        torch._foreach_div_(den, bc2 ** 0.5)
+        torch._foreach_add_(den, hpl["eps"])
+        u = torch._foreach_div(fm, bc1)
+        torch._foreach_div_(u, den)
+        torch._foreach_add_(u, fw, alpha=hpl["weight_decay"])
+        wn, un = torch.stack(torch._foreach_norm(fw)), torch.stack(torch._foreach_norm(u))
+        scale = torch.where((wn > 0) & (un > 0), wn / un, torch.ones_like(wn)).mul_(-hpl["lr"])
+        torch._foreach_mul_(u, list(scale.unbind()))
+        torch._foreach_add_(fw, u)
+    t = timeit(foreach_lamb)
+    report("torch _foreach LAMB (context)", t, 10 * 4 * n, "161 tensors, host-side step count")
+    del fw, fg, fm, fv, wa, ga, ma, va
     u = torch.zeros(n, device=dev)
     t = timeit(lambda: ops.momentum_correct_(u, gr, w, chunks, 0, chunks.numel() // 2, hp))
     report("momentum_correct (u,g,w)", t, 5 * 4 * n)

@@ -1002,6 +1002,127 @@ def fused_adam_(w: torch.Tensor, m: torch.Tensor, v: torch.Tensor, g: torch.Tens
             g[start:start + ln].zero_()
 
 
+class LambWorkspace:
+    """What ``fused_lamb_`` needs beside the arenas, built once per chunk table.
+
+    ``seg_range``: int32 ``[2 * nseg]``, the first chunk and the number of
+    chunks of every tensor; ``part``: float64 ``[2 * nchunks]``, the per-chunk
+    sums of w^2 and u^2 of the current step; ``trust``: float32 ``[nseg]``,
+    the trust ratios of the last step.  ``segments``: the decoded table
+    (CPU fallback).
+    """
+
+    def __init__(self, seg_range, part, trust, segments):
+        self.seg_range = seg_range
+        self.part = part
+        self.trust = trust
+        self.segments = segments
+        self.nchunks = part.numel() // 2
+        self.nseg = trust.numel()
+
+
+def make_lamb_workspace(chunks: torch.Tensor, device) -> LambWorkspace:
+    """Decode the chunk table on the host ONCE (a step never copies it back: a
+    precondition for graph capture).  A tensor's chunks must be consecutive in
+    the table -- its partial sums are added in table order -- and its id must
+    fit the table's 15-bit field."""
+    table = chunks.view(-1, 2).cpu().tolist()
+    decoded = []
+    first: dict = {}
+    count: dict = {}
+    for ci, (start, word) in enumerate(table):
+        seg = (word >> 48) & 0xFFFF
+        if seg > 0x7FFF:
+            raise ValueError("chunk %d: segment id %d exceeds the chunk table's 15-bit field" % (ci, seg))
+        if seg not in first:
+            first[seg], count[seg] = ci, 0
+        elif first[seg] + count[seg] != ci:
+            raise ValueError("segment %d: its chunks are not consecutive in the chunk table (chunk %d follows chunk "
+                             "%d)" % (seg, ci, first[seg] + count[seg] - 1))
+        count[seg] += 1
+        decoded.append((start, word & 0xFFFFFFFF, (word >> 32) & 0xFFFF, seg))
+    nseg = max(first) + 1 if first else 0
+    rng = [0] * (2 * nseg)
+    for seg, f in first.items():
+        rng[2 * seg], rng[2 * seg + 1] = f, count[seg]
+    return LambWorkspace(torch.tensor(rng, dtype=torch.int32, device=device),
+                         torch.zeros(2 * len(table), dtype=torch.float64, device=device),
+                         torch.ones(nseg, dtype=torch.float32, device=device), decoded)
+
+
+def fused_lamb_(w: torch.Tensor, m: torch.Tensor, v: torch.Tensor, g: torch.Tensor, chunks: torch.Tensor,
+                groups: Sequence[dict], step: torch.Tensor, ws: LambWorkspace, zero_grad: bool = True,
+                grad_scale: Optional[torch.Tensor] = None, w_bf16: Optional[torch.Tensor] = None,
+                lr_mult: Optional[torch.Tensor] = None) -> None:
+    """LAMB (You et al., 2020) over the chunk table: Adam's moments,
+    ``u = mhat / (sqrt(vhat) + eps) + wd * w`` and per tensor (segment of the
+    table) ``trust = ||w|| / ||u||``; ``w -= lr * lr_mult * trust * u``.
+
+    groups: dicts with lr, betas, eps, weight_decay, adapt (False: trust = 1,
+    which is AdamW with decoupled decay) and trust_clip (upper bound of the
+    ratio; 0 / None: none).  ``step``, ``grad_scale``, ``w_bf16``, ``lr_mult``
+    and the ``eps > 0`` rule as in ``fused_adam_``.  ``ws``: the workspace of
+    THIS chunk table (``make_lamb_workspace``); ``ws.trust`` holds the step's
+    ratios afterwards.  On the GPU: the step tick and three launches, the norms
+    reduced in an order that depends on the table alone (no atomics), so
+    replicas stay bit-identical.
+    """
+    if any(not float(p["eps"]) > 0.0 for p in groups):
+        raise ValueError("fused_lamb_ needs eps > 0 in every group (eps = 0 turns zero slots into 0 / 0)")
+    if ws.nchunks != chunks.numel() // 2:
+        raise ValueError("the LAMB workspace was built for a table of %d chunks, not %d" % (ws.nchunks,
+                                                                                           chunks.numel() // 2))
+    clip = [float(p.get("trust_clip") or 0.0) for p in groups]
+    if w.is_cuda:
+        require_native(w)
+        _ops().fused_lamb(w, m, v, g, chunks, step, ws.seg_range, ws.part, ws.trust, [float(p["lr"]) for p in groups],
+                          [float(p["betas"][0]) for p in groups], [float(p["betas"][1]) for p in groups],
+                          [float(p["eps"]) for p in groups], [float(p.get("weight_decay", 0.0)) for p in groups],
+                          [int(bool(p.get("adapt", True))) for p in groups], clip, bool(zero_grad), grad_scale,
+                          w_bf16, lr_mult)
+        return
+    step += 1
+    t = float(step)
+    gs = float(grad_scale) if grad_scale is not None else 1.0
+    lm = float(lr_mult) if lr_mult is not None else 1.0
+
+    def direction(start, ln, p):
+        b1, b2 = float(p["betas"][0]), float(p["betas"][1])
+        denom = (v[start:start + ln].sqrt() / math.sqrt(1.0 - b2 ** t)).add_(float(p["eps"]))
+        return (m[start:start + ln] / (1.0 - b1 ** t)).div_(denom).add_(w[start:start + ln],
+                                                                        alpha=float(p.get("weight_decay", 0.0)))
+
+    sumsq = torch.zeros(2 * ws.nseg, dtype=torch.float64)
+    for start, ln, gi, seg in ws.segments:
+        p = groups[gi]
+        b1, b2 = float(p["betas"][0]), float(p["betas"][1])
+        d = g[start:start + ln] * gs
+        m[start:start + ln].lerp_(d, 1.0 - b1)
+        v[start:start + ln].mul_(b2).addcmul_(d, d, value=1.0 - b2)
+        sumsq[2 * seg] += (w[start:start + ln].double() ** 2).sum()
+        sumsq[2 * seg + 1] += (direction(start, ln, p).double() ** 2).sum()
+    ws.trust.fill_(1.0)
+    for seg in range(ws.nseg):
+        first, n = int(ws.seg_range[2 * seg]), int(ws.seg_range[2 * seg + 1])
+        if n == 0:
+            continue
+        gi = ws.segments[first][2]
+        wn, un = float(sumsq[2 * seg].sqrt().float()), float(sumsq[2 * seg + 1].sqrt().float())
+        trust = wn / un if groups[gi].get("adapt", True) and wn > 0 and un > 0 else 1.0
+        if clip[gi] > 0:
+            trust = min(trust, clip[gi])
+        ws.trust[seg] = trust
+    for start, ln, gi, seg in ws.segments:
+        p = groups[gi]
+        ws_ = w[start:start + ln]
+        ws_.add_(direction(start, ln, p), alpha=-float(torch.tensor(float(p["lr"]) * lm * float(ws.trust[seg]),
+                                                                  dtype=torch.float32)))
+        if w_bf16 is not None:
+            w_bf16[start:start + ln].copy_(ws_)
+        if zero_grad:
+            g[start:start + ln].zero_()
+
+
 def segmented_sumsq_(w: torch.Tensor, g: torch.Tensor, chunks: torch.Tensor, out: torch.Tensor) -> None:
     if w.is_cuda:
         require_native(w)

@@ -357,6 +357,85 @@ void fused_adam(at::Tensor w, at::Tensor m, at::Tensor v, at::Tensor g, at::Tens
   gk::fused_adam(a, cur_stream(w));
 }
 
+// seg_range / part / trust: the workspace ops.make_lamb_workspace built for this chunk table
+void fused_lamb(at::Tensor w, at::Tensor m, at::Tensor v, at::Tensor g, at::Tensor chunks, at::Tensor step,
+                at::Tensor seg_range, at::Tensor part, at::Tensor trust, std::vector<double> lr,
+                std::vector<double> beta1, std::vector<double> beta2, std::vector<double> eps,
+                std::vector<double> weight_decay, std::vector<int64_t> adapt, std::vector<double> trust_clip,
+                bool zero_grad, c10::optional<at::Tensor> grad_scale, c10::optional<at::Tensor> w_bf16,
+                c10::optional<at::Tensor> lr_mult, int64_t passes) {
+  check_f32(w, "w");
+  check_f32(m, "m");
+  check_f32(v, "v");
+  check_f32(g, "g");
+  check_f32(step, "step");
+  check_f32(trust, "trust");
+  check_chunks(chunks);
+  check_dev(seg_range, "seg_range");
+  check_dev(part, "part");
+  const size_t ng = lr.size();
+  TORCH_CHECK(ng >= 1 && ng <= (size_t)gk::kMaxGroups, "1..8 param groups supported");
+  TORCH_CHECK(beta1.size() == ng && beta2.size() == ng && eps.size() == ng && weight_decay.size() == ng &&
+                  adapt.size() == ng && trust_clip.size() == ng,
+              "hyper-parameter lists must have one entry per group");
+  TORCH_CHECK(w.numel() == g.numel() && m.numel() == w.numel() && v.numel() == w.numel(),
+              "w/m/v/g size mismatch");
+  TORCH_CHECK(step.numel() == 1, "step must be one fp32 device scalar");
+  TORCH_CHECK(((reinterpret_cast<uintptr_t>(w.data_ptr()) | reinterpret_cast<uintptr_t>(g.data_ptr()) |
+                reinterpret_cast<uintptr_t>(m.data_ptr()) | reinterpret_cast<uintptr_t>(v.data_ptr())) & 15) == 0,
+              "arenas must be 16-byte aligned");
+  const int64_t nchunks = chunks.numel() / 2;
+  const int64_t nseg = trust.numel();
+  TORCH_CHECK(seg_range.scalar_type() == at::kInt && seg_range.is_contiguous() && seg_range.numel() == 2 * nseg,
+              "seg_range must be int32[2 * nseg]");
+  TORCH_CHECK(part.scalar_type() == at::kDouble && part.is_contiguous() && part.numel() >= 2 * nchunks,
+              "part must be float64[2 * nchunks]: the workspace belongs to another chunk table");
+  TORCH_CHECK(trust.is_contiguous(), "trust must be contiguous");
+  gk::LambArgs a;
+  a.w = w.data_ptr<float>();
+  a.m = m.data_ptr<float>();
+  a.v = v.data_ptr<float>();
+  a.g = g.data_ptr<float>();
+  a.step = step.data_ptr<float>();
+  for (size_t i = 0; i < ng; ++i) {
+    a.groups[i].lr = lr[i];
+    a.groups[i].beta1 = beta1[i];
+    a.groups[i].beta2 = beta2[i];
+    TORCH_CHECK(eps[i] > 0.0, "eps must be positive (eps = 0 turns the zero padding slots into 0 / 0)");
+    a.groups[i].eps = eps[i];
+    a.groups[i].weight_decay = weight_decay[i];
+    a.groups[i].trust_clip = trust_clip[i];
+    a.groups[i].adapt = (int)adapt[i];
+    a.groups[i].pad0 = 0;
+  }
+  for (size_t i = ng; i < (size_t)gk::kMaxGroups; ++i) a.groups[i] = gk::LambGroup{0, 0, 0, 0, 0, 0, 0, 0};
+  a.ngroups = (int)ng;
+  a.chunks = reinterpret_cast<const gk::Chunk*>(chunks.data_ptr<int64_t>());
+  a.nchunks = (int)nchunks;
+  a.zero_grad = zero_grad ? 1 : 0;
+  a.seg_range = seg_range.data_ptr<int32_t>();
+  a.nseg = (int)nseg;
+  a.part = part.data_ptr<double>();
+  a.trust = trust.data_ptr<float>();
+  a.passes = (int)passes;
+  if (grad_scale.has_value() && grad_scale->defined()) {
+    check_f32(*grad_scale, "grad_scale");
+    a.grad_scale = grad_scale->data_ptr<float>();
+  }
+  if (w_bf16.has_value() && w_bf16->defined()) {
+    TORCH_CHECK(w_bf16->scalar_type() == at::kBFloat16 && w_bf16->numel() == w.numel() && w_bf16->is_contiguous() &&
+                    (reinterpret_cast<uintptr_t>(w_bf16->data_ptr()) & 15) == 0,
+                "w_bf16 must be a 16-byte aligned contiguous bf16 arena of w's size");
+    a.w_bf16 = reinterpret_cast<uint16_t*>(w_bf16->data_ptr());
+  }
+  if (lr_mult.has_value() && lr_mult->defined()) {
+    check_f32(*lr_mult, "lr_mult");
+    a.lr_mult = lr_mult->data_ptr<float>();
+  }
+  c10::DeviceGuard guard(w.device());
+  gk::fused_lamb(a, cur_stream(w));
+}
+
 void segmented_sumsq(at::Tensor w, at::Tensor g, at::Tensor chunks, at::Tensor out) {
   check_f32(w, "w");
   check_f32(g, "g");
@@ -2117,6 +2196,11 @@ TORCH_LIBRARY(gksgd, m) {
       "fused_adam(Tensor(a!) w, Tensor(b!) m, Tensor(c!) v, Tensor(d!) g, Tensor chunks, Tensor(e!) step, float[] lr, "
       "float[] beta1, float[] beta2, float[] eps, float[] weight_decay, int[] decoupled, bool zero_grad, "
       "Tensor? grad_scale=None, Tensor(f!)? w_bf16=None, Tensor? lr_mult=None) -> ()");
+  m.def(
+      "fused_lamb(Tensor(a!) w, Tensor(b!) m, Tensor(c!) v, Tensor(d!) g, Tensor chunks, Tensor(e!) step, "
+      "Tensor seg_range, Tensor(f!) part, Tensor(g!) trust, float[] lr, float[] beta1, float[] beta2, float[] eps, "
+      "float[] weight_decay, int[] adapt, float[] trust_clip, bool zero_grad, Tensor? grad_scale=None, "
+      "Tensor(h!)? w_bf16=None, Tensor? lr_mult=None, int passes=7) -> ()");
   m.def("segmented_sumsq(Tensor w, Tensor g, Tensor chunks, Tensor(a!) out) -> ()");
   m.def(
       "fused_lars(Tensor(a!) w, Tensor(b!) m, Tensor g, Tensor chunks, Tensor seg_sumsq, float[] lr, "
@@ -2290,6 +2374,7 @@ TORCH_LIBRARY_IMPL(gksgd, CUDA, m) {
   m.impl("sign_bucket_decompress", &sign_bucket_decompress);
   m.impl("fused_sgd", &fused_sgd);
   m.impl("fused_adam", &fused_adam);
+  m.impl("fused_lamb", &fused_lamb);
   m.impl("segmented_sumsq", &segmented_sumsq);
   m.impl("fused_lars", &fused_lars);
   m.impl("clip_grad_norm", &clip_grad_norm);

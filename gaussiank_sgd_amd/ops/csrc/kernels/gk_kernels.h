@@ -234,6 +234,40 @@ struct AdamArgs {
 // workgroups read the new count for the bias corrections.  No host read.
 void fused_adam(const AdamArgs& a, hipStream_t stream);
 
+// LAMB: Adam's moments, u = mhat / (sqrt(vhat) + eps) + wd * w, and per tensor
+// (segment of the chunk table) trust = ||w|| / ||u||; w -= lr * trust * u.
+struct LambGroup {
+  double lr, beta1, beta2, eps, weight_decay;
+  double trust_clip;  // upper bound of the trust ratio; 0: none
+  int adapt;          // 0: trust = 1 (AdamW with decoupled decay)
+  int pad0;
+};
+struct LambArgs {
+  float* w = nullptr;
+  float* m = nullptr;        // exp_avg
+  float* v = nullptr;        // exp_avg_sq
+  float* g = nullptr;
+  const Chunk* chunks = nullptr;
+  int nchunks = 0;
+  LambGroup groups[kMaxGroups];
+  int ngroups = 0;
+  int zero_grad = 1;
+  float* step = nullptr;              // device step count, as AdamArgs::step
+  const float* grad_scale = nullptr;
+  uint16_t* w_bf16 = nullptr;
+  const float* lr_mult = nullptr;
+  const int32_t* seg_range = nullptr; // [2 * nseg]: first chunk, number of chunks of every tensor
+  int nseg = 0;
+  double* part = nullptr;             // [2 * nchunks] workspace: per-chunk sum of w^2, of u^2
+  float* trust = nullptr;             // [nseg] out: this step's trust ratios
+  int passes = 7;                     // bit 0: tick + moments, 1: trust, 2: apply (bench/kernels.py times them apart)
+};
+// Four launches on `stream`: the step tick, lamb_moments_kernel (m, v and the
+// chunk partials; w and g untouched), lamb_trust_kernel (one wave per tensor,
+// fixed summation order), lamb_apply_kernel (w, bf16 shadow, zeroed g).
+// Launch boundaries only: no atomics, no in-grid barriers, no host read.
+void fused_lamb(const LambArgs& a, hipStream_t stream);
+
 // DGC momentum correction over a chunk range: u = mu*u + g + wd*w; g = u.
 struct McArgs {
   float* u = nullptr;

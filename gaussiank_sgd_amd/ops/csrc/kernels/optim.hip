@@ -12,6 +12,11 @@
 //                    scalars; the step count is a device scalar bumped by a
 //                    one-thread launch ahead of the update, so eager steps and
 //                    HIP-graph replays take one path with no host read.
+//   fused_lamb       LAMB (You et al. 2020): the Adam direction u with decoupled
+//                    decay, scaled per tensor by ||w|| / ||u||.  Three launches
+//                    after the step tick (moments + chunk partials, one wave per
+//                    tensor for the ratio, apply); the norms are reduced in a
+//                    fixed order, so replicas stay bit-identical.
 //   segmented_sumsq  per-tensor ||w||^2, ||g||^2 (LARS trust ratios)
 //   fused_lars       K13: lars.py:67-134 (trust ratio clamp [0,50], grad clamp
 //                    +-10, acceleration buffer initialised to ones)
@@ -172,6 +177,173 @@ __global__ __launch_bounds__(kBlock) void fused_adam_kernel(AdamArgs a) {
     w[i] = wn;
     m[i] = mv;
     v[i] = vv;
+    if (a.zero_grad) g[i] = 0.f;
+    if (a.w_bf16) a.w_bf16[c.start + i] = f2bf(wn);
+  }
+}
+
+// ---- LAMB ---------------------------------------------------------------------
+// Per-workgroup constants of one chunk's param group at the current step.
+struct LambCoef {
+  float omb1, beta2, omb2;   // 1 - beta1, beta2, 1 - beta2
+  float bc1;                 // 1 - beta1^t
+  float bc2_sqrt;            // sqrt(1 - beta2^t)
+  float eps, wd;
+};
+
+// thread 0 of the workgroup; bias corrections in double from the device step count, as fused_adam_kernel
+__device__ __forceinline__ LambCoef lamb_coef(const LambGroup& p, const float* step) {
+  const double t = (double)*step;
+  LambCoef k;
+  k.omb1 = (float)(1.0 - p.beta1);
+  k.beta2 = (float)p.beta2;
+  k.omb2 = (float)(1.0 - p.beta2);
+  k.bc1 = (float)(1.0 - pow(p.beta1, t));
+  k.bc2_sqrt = (float)sqrt(1.0 - pow(p.beta2, t));
+  k.eps = (float)p.eps;
+  k.wd = (float)p.weight_decay;
+  return k;
+}
+
+// The moment update of adam_elem (same forms).
+__device__ __forceinline__ void lamb_moments(float& m, float& v, float g, const LambCoef& k, float gs) {
+  const float d = g * gs;
+  m = fmaf(k.omb1, d - m, m);
+  v = fmaf(k.omb2 * d, d, k.beta2 * v);
+}
+
+// The update direction from the UPDATED moments; both streaming passes call
+// this, so the u whose norm was taken is the u that is applied.  IEEE sqrt and
+// divisions for the reason given at adam_elem; a slot with w = m = v = 0
+// (padding) gives 0 / (0 + eps) + wd * 0 = 0 because eps > 0.
+__device__ __forceinline__ float lamb_u(float w, float m, float v, const LambCoef& k) {
+  const float denom = sqrtf(v) / k.bc2_sqrt + k.eps;
+  return fmaf(k.wd, w, (m / k.bc1) / denom);
+}
+
+// Pass 1: m, v updated in place; the chunk's sum of w^2 and of u^2 to part[2 * chunk], part[2 * chunk + 1].
+// Each lane adds at most kChunkElems / kBlock = 64 squares in fp32; everything above that is double.
+__global__ __launch_bounds__(kBlock) void lamb_moments_kernel(LambArgs a) {
+  const Chunk c = a.chunks[blockIdx.x];
+  __shared__ LambCoef sk;
+  __shared__ double sh[kWavesPerBlock];
+  if (threadIdx.x == 0) sk = lamb_coef(a.groups[c.group], a.step);
+  __syncthreads();
+  const LambCoef k = sk;
+  const float gs = a.grad_scale ? *a.grad_scale : 1.f;
+  const float* w = a.w + c.start;
+  float* m = a.m + c.start;
+  float* v = a.v + c.start;
+  const float* g = a.g + c.start;
+  const int n4 = c.len >> 2;
+  const float4* w4 = reinterpret_cast<const float4*>(w);
+  float4* m4 = reinterpret_cast<float4*>(m);
+  float4* v4 = reinterpret_cast<float4*>(v);
+  const float4* g4 = reinterpret_cast<const float4*>(g);
+  float sw = 0.f, su = 0.f;
+  for (int i = threadIdx.x; i < n4; i += kBlock) {
+    const float4 wv = w4[i];
+    float4 mv = m4[i];
+    float4 vv = v4[i];
+    const float4 gv = g4[i];
+    lamb_moments(mv.x, vv.x, gv.x, k, gs);
+    lamb_moments(mv.y, vv.y, gv.y, k, gs);
+    lamb_moments(mv.z, vv.z, gv.z, k, gs);
+    lamb_moments(mv.w, vv.w, gv.w, k, gs);
+    m4[i] = mv;
+    v4[i] = vv;
+    const float ux = lamb_u(wv.x, mv.x, vv.x, k), uy = lamb_u(wv.y, mv.y, vv.y, k);
+    const float uz = lamb_u(wv.z, mv.z, vv.z, k), uw = lamb_u(wv.w, mv.w, vv.w, k);
+    sw += (wv.x * wv.x + wv.y * wv.y) + (wv.z * wv.z + wv.w * wv.w);
+    su += (ux * ux + uy * uy) + (uz * uz + uw * uw);
+  }
+  for (int i = (n4 << 2) + threadIdx.x; i < c.len; i += kBlock) {
+    float mv = m[i], vv = v[i];
+    const float wv = w[i];
+    lamb_moments(mv, vv, g[i], k, gs);
+    m[i] = mv;
+    v[i] = vv;
+    const float u = lamb_u(wv, mv, vv, k);
+    sw += wv * wv;
+    su += u * u;
+  }
+  const double bw = block_sum((double)sw, sh);
+  const double bu = block_sum((double)su, sh);
+  if (threadIdx.x == 0) {
+    a.part[2 * (int64_t)blockIdx.x] = bw;
+    a.part[2 * (int64_t)blockIdx.x + 1] = bu;
+  }
+}
+
+// Pass 2: one wave per tensor.  Lane l adds the partials of chunks first + l, first + l + 64, ... in ascending
+// order, then the xor butterfly of wave_sum: the order depends on the table alone, never on arrival.
+__global__ __launch_bounds__(kBlock) void lamb_trust_kernel(LambArgs a) {
+  const int seg = blockIdx.x * kWavesPerBlock + wave_id();
+  if (seg >= a.nseg) return;
+  const int first = a.seg_range[2 * seg];
+  int n = a.seg_range[2 * seg + 1];
+  if (first < 0 || first + n > a.nchunks) n = 0;   // a workspace of another table: read nothing outside part
+  double sw = 0.0, su = 0.0;
+  for (int c = first + lane_id(); c < first + n; c += kWave) {
+    sw += a.part[2 * (int64_t)c];
+    su += a.part[2 * (int64_t)c + 1];
+  }
+  sw = wave_sum(sw);
+  su = wave_sum(su);
+  if (lane_id() != 0) return;
+  float trust = 1.f;
+  if (n > 0) {
+    const LambGroup p = a.groups[a.chunks[first].group];
+    const float wn = (float)sqrt(sw), un = (float)sqrt(su);
+    if (p.adapt && wn > 0.f && un > 0.f) trust = wn / un;
+    if (p.trust_clip > 0.0) trust = fminf(trust, (float)p.trust_clip);
+  }
+  a.trust[seg] = trust;
+}
+
+// Pass 3: w -= (lr * lr_mult * trust[seg]) * u, u recomputed from the updated moments.
+__global__ __launch_bounds__(kBlock) void lamb_apply_kernel(LambArgs a) {
+  const Chunk c = a.chunks[blockIdx.x];
+  __shared__ LambCoef sk;
+  __shared__ float s_slr;
+  if (threadIdx.x == 0) {
+    const LambGroup p = a.groups[c.group];
+    sk = lamb_coef(p, a.step);
+    double lr = p.lr;
+    if (a.lr_mult) lr *= (double)*a.lr_mult;   // lr schedule of a captured graph
+    const float trust = (c.seg >= 0 && c.seg < a.nseg) ? a.trust[c.seg] : 1.f;
+    s_slr = (float)(lr * (double)trust);
+  }
+  __syncthreads();
+  const LambCoef k = sk;
+  const float nslr = -s_slr;
+  float* w = a.w + c.start;
+  const float* m = a.m + c.start;
+  const float* v = a.v + c.start;
+  float* g = a.g + c.start;
+  const int n4 = c.len >> 2;
+  float4* w4 = reinterpret_cast<float4*>(w);
+  const float4* m4 = reinterpret_cast<const float4*>(m);
+  const float4* v4 = reinterpret_cast<const float4*>(v);
+  for (int i = threadIdx.x; i < n4; i += kBlock) {
+    float4 wv = w4[i];
+    const float4 mv = m4[i];
+    const float4 vv = v4[i];
+    wv.x = fmaf(nslr, lamb_u(wv.x, mv.x, vv.x, k), wv.x);
+    wv.y = fmaf(nslr, lamb_u(wv.y, mv.y, vv.y, k), wv.y);
+    wv.z = fmaf(nslr, lamb_u(wv.z, mv.z, vv.z, k), wv.z);
+    wv.w = fmaf(nslr, lamb_u(wv.w, mv.w, vv.w, k), wv.w);
+    w4[i] = wv;
+    if (a.zero_grad) reinterpret_cast<float4*>(g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (a.w_bf16) {
+      const uint32_t lo = (uint32_t)f2bf(wv.x) | ((uint32_t)f2bf(wv.y) << 16);
+      const uint32_t hi = (uint32_t)f2bf(wv.z) | ((uint32_t)f2bf(wv.w) << 16);
+      reinterpret_cast<uint2*>(a.w_bf16 + c.start)[i] = make_uint2(lo, hi);
+    }
+  }
+  for (int i = (n4 << 2) + threadIdx.x; i < c.len; i += kBlock) {
+    const float wn = fmaf(nslr, lamb_u(w[i], m[i], v[i], k), w[i]);
+    w[i] = wn;
     if (a.zero_grad) g[i] = 0.f;
     if (a.w_bf16) a.w_bf16[c.start + i] = f2bf(wn);
   }
@@ -369,6 +541,18 @@ void fused_adam(const AdamArgs& a, hipStream_t s) {
   if (a.nchunks <= 0) return;
   hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, s, a.step);
   hipLaunchKernelGGL(fused_adam_kernel, dim3(a.nchunks), dim3(kBlock), 0, s, a);
+}
+
+void fused_lamb(const LambArgs& a, hipStream_t s) {
+  if (a.nchunks <= 0 || a.nseg <= 0) return;
+  if (a.passes & 1) {
+    hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, s, a.step);
+    hipLaunchKernelGGL(lamb_moments_kernel, dim3(a.nchunks), dim3(kBlock), 0, s, a);
+  }
+  if (a.passes & 2)
+    hipLaunchKernelGGL(lamb_trust_kernel, dim3((a.nseg + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kBlock), 0, s,
+                       a);
+  if (a.passes & 4) hipLaunchKernelGGL(lamb_apply_kernel, dim3(a.nchunks), dim3(kBlock), 0, s, a);
 }
 
 void momentum_correct(const McArgs& a, hipStream_t s) {

@@ -1,4 +1,4 @@
-"""Optimizers: LARS (lars.py parity) and the SGD parameter-group helper of the
+"""Optimizers: LARS (lars.py parity), LAMB and the SGD parameter-group helper of the
 reference trainer (dl_trainer.py:212-228)."""
 from __future__ import annotations
 
@@ -6,6 +6,7 @@ from typing import List
 
 import torch
 
+from .lamb import LAMB
 from .lars import LARS
 
 
@@ -22,4 +23,4 @@ def sgd_param_groups(net: torch.nn.Module, weight_decay: float) -> List[dict]:
     return [{"params": no_decay, "weight_decay": 0.0}, {"params": decay, "weight_decay": weight_decay}]
 
 
-__all__ = ["LARS", "sgd_param_groups"]
+__all__ = ["LAMB", "LARS", "sgd_param_groups"]

@@ -30,7 +30,9 @@ MI355X execution model (what is different, and why):
     arena in the same pass.  ``torch.optim.Adam`` / ``AdamW`` get the same
     one-launch update (``ops.fused_adam_``); their step count is ONE fp32
     device scalar that every ``state[p]["step"]`` aliases, incremented on the
-    device, so a captured HIP graph follows it.
+    device, so a captured HIP graph follows it.  ``optim.LAMB`` shares that
+    state and runs ``ops.fused_lamb_`` (per-tensor trust ratios reduced in a
+    fixed order; ``trust_ratios()``).
 """
 from __future__ import annotations
 
@@ -95,10 +97,13 @@ class _DistributedOptimizer(torch.optim.Optimizer):
         opts = dict(_gk_opts or {})
         defaults = opts.pop("defaults", {}) or {}
         # torch.optim.AdamW sets decoupled_weight_decay itself and does not take it back as an
-        # argument; any other default its class refuses still raises
-        if "decoupled_weight_decay" in defaults and "decoupled_weight_decay" not in \
-                inspect.signature(self.__class__.__mro__[1].__init__).parameters:
-            defaults = {k: v for k, v in defaults.items() if k != "decoupled_weight_decay"}
+        # argument, and Optimizer.__setstate__ (every load_state_dict) adds differentiable=False to
+        # the defaults of classes that do not take it (LAMB, LARS); any other default its class
+        # refuses still raises
+        takes = inspect.signature(self.__class__.__mro__[1].__init__).parameters
+        for own in ("decoupled_weight_decay", "differentiable"):
+            if own in defaults and own not in takes and (own != "differentiable" or not defaults[own]):
+                defaults = {k: v for k, v in defaults.items() if k != own}
         super(self.__class__, self).__init__(params, **defaults)
         self._compression = compression
         self._sparse = is_sparse
@@ -1033,6 +1038,7 @@ class _DistributedOptimizer(torch.optim.Optimizer):
         base = self._base_cls
         if not self._fused_optim or base is None:
             return
+        from ..optim.lamb import LAMB
         from ..optim.lars import LARS
         in_arena = all(p in self._parameter_names for g in self.param_groups for p in g["params"]
                        if p.requires_grad)
@@ -1053,8 +1059,14 @@ class _DistributedOptimizer(torch.optim.Optimizer):
             self._adam_capable = True
             # the step count of every parameter: one device scalar (torch's capturable convention)
             self._adam_step = torch.zeros((), dtype=torch.float32, device=self._device)
+        elif base is LAMB:
+            # Adam's state (one device step scalar, both moment arenas) with another update
+            self._fused_kind = "lamb"
+            self._adam_capable = True
+            self._adam_step = torch.zeros((), dtype=torch.float32, device=self._device)
         else:
             return
+        self._adam_kind = self._fused_kind    # what load_state_dict / broadcast_state restore
         group_of_key = {}
         for gi, g in enumerate(self.param_groups):
             for p in g["params"]:
@@ -1083,6 +1095,10 @@ class _DistributedOptimizer(torch.optim.Optimizer):
         self._group_first = [True] * len(self.param_groups)
         if self._fused_kind == "lars":
             self._seg_sumsq = torch.zeros(2 * self._nseg, dtype=torch.float64, device=self._device)
+        elif self._fused_kind == "lamb":
+            self._lamb_ws = ops.make_lamb_workspace(self._chunks, self._device)
+            # segment ids follow arena.segments(): bucket by bucket, key by key
+            self._lamb_seg_names = [k for b in self._arena.buckets for k in b.keys]
 
     def _adopt_state(self):
         """Point optimizer state at arena views (after first step / load_state_dict)."""
@@ -1121,7 +1137,7 @@ class _DistributedOptimizer(torch.optim.Optimizer):
                 if buf is not None and buf.data_ptr() != view.data_ptr():
                     view.copy_(buf)
                 st["acceleration"] = view
-        elif self._fused_kind == "adam":
+        elif self._fused_kind in ("adam", "lamb"):
             params = [p for g in self.param_groups for p in g["params"] if p in self._parameter_names]
             shared = self._adam_step
             # step counts handed in (factory / load_state_dict); a parameter without state has taken none
@@ -1199,6 +1215,14 @@ class _DistributedOptimizer(torch.optim.Optimizer):
             if any(self._group_first):
                 self._group_first = [False] * len(self._group_first)
                 self._adopt_state()
+        elif self._fused_kind == "lamb":
+            # the step tick, the moments with per-chunk norm partials, one wave per tensor for the
+            # trust ratio, the update: launch boundaries only, so a captured graph replays it as it is
+            groups = [{"lr": g["lr"], "betas": g["betas"], "eps": g["eps"], "weight_decay": g.get("weight_decay", 0.0),
+                       "adapt": g.get("adapt", True), "trust_clip": g.get("trust_clip")} for g in self.param_groups]
+            ops.fused_lamb_(arena.weights, arena.momentum, arena.second_moment, arena.grads, self._chunks, groups,
+                            self._adam_step, self._lamb_ws, zero_grad=self._zero_grad_in_step,
+                            w_bf16=getattr(arena, "shadow", None), lr_mult=self._lr_mult)
         elif self._fused_kind == "adam":
             # one tick of the device step count + one update launch; the bias
             # corrections are derived on the device, so this is also what a
@@ -1235,7 +1259,7 @@ class _DistributedOptimizer(torch.optim.Optimizer):
             self._exchanger.check()   # native engine: raise if its watchdog aborted a hung collective
         if not self.local:
             self.synchronize()
-        if self._fused_kind == "adam" and (self._state_dirty or self._arena.second_moment is None):
+        if self._fused_kind in ("adam", "lamb") and (self._state_dirty or self._arena.second_moment is None):
             with torch.no_grad():
                 self._adopt_state()    # may fall back to the unfused update (differing step counts)
         if self._fused_kind is not None:
@@ -1264,7 +1288,7 @@ class _DistributedOptimizer(torch.optim.Optimizer):
 
     def state_dict(self):
         sd = super(self.__class__, self).state_dict()
-        if self._fused_kind == "adam":
+        if self._fused_kind in ("adam", "lamb"):
             # every state[p]["step"] is the one device scalar: hand out one counter
             # per parameter, as a plain torch.optim.Adam(W) that loads this expects
             sd["state"] = {k: ({**st, "step": st["step"].clone()} if torch.is_tensor(st.get("step")) else st)
@@ -1275,7 +1299,7 @@ class _DistributedOptimizer(torch.optim.Optimizer):
         super(self.__class__, self).load_state_dict(state_dict)
         self._state_dirty = True
         if self._adam_capable:
-            self._fused_kind = "adam"    # the new state decides again (differing step counts drop it)
+            self._fused_kind = self._adam_kind    # the new state decides again (differing step counts drop it)
         if self._fused_kind is not None:
             with torch.no_grad():
                 self._adopt_state()
@@ -1380,14 +1404,14 @@ class _DistributedOptimizer(torch.optim.Optimizer):
             if self._rank != root_rank:
                 for p in params:           # the root's state replaces whatever this rank held,
                     self.state.pop(p, None)
-                self._fused_kind = "adam"  # and with it this rank's own reason to run unfused
+                self._fused_kind = self._adam_kind  # and with it this rank's own reason to run unfused
                 self._state_dirty = True
-            if self._fused_kind == "adam" and (self._state_dirty or self._arena.second_moment is None):
+            if self._fused_kind == self._adam_kind and (self._state_dirty or self._arena.second_moment is None):
                 self._adopt_state()    # root: buffers -> arena views; others: zero arenas
             # the root's kind decides for every rank: one sequence of collectives
-            if not broadcast_object(self._fused_kind == "adam", root_rank):
+            if not broadcast_object(self._fused_kind == self._adam_kind, root_rank):
                 # the root's parameters are at different steps: every rank keeps torch's update
-                if self._fused_kind == "adam":
+                if self._fused_kind == self._adam_kind:
                     self._fused_kind = None
                     for p in params:
                         self.state[p]["step"] = self.state[p]["step"].clone()
@@ -1397,6 +1421,14 @@ class _DistributedOptimizer(torch.optim.Optimizer):
             broadcast_(self._arena.second_moment, root_rank)
             broadcast_(self._adam_step.view(1), root_rank)
         self._state_dirty = False
+
+    def trust_ratios(self) -> Dict[str, torch.Tensor]:
+        """LAMB's trust ratio of every parameter at the last fused step: name ->
+        0-d fp32 view of the device buffer (no host sync until a value is read;
+        all ones before the first step)."""
+        if self._fused_kind != "lamb":
+            raise RuntimeError("trust_ratios() needs the fused LAMB update (optim.LAMB in DistributedOptimizer)")
+        return {name: self._lamb_ws.trust[i] for i, name in enumerate(self._lamb_seg_names)}
 
     @property
     def arena(self) -> GradArena:

@@ -16,7 +16,8 @@ understood).  New flags: ``--synthetic`` (always on: no datasets offline),
 ``--amp bf16``, ``--channels-last``, ``--density-warmup/--no-density-warmup``,
 ``--deterministic``, ``--max-iters``, ``--compress-single-rank``,
 ``--optimizer {sgd,adam,adamw}`` with ``--adam-beta1 --adam-beta2 --adam-eps
---weight-decay``.
+--weight-decay``, ``--trust-ratio`` / ``--trust-clip`` (LAMB: AdamW with
+per-tensor trust ratios).
 """
 from __future__ import annotations
 
@@ -41,7 +42,7 @@ def ssgd(dnn, dataset, data_dir, nworkers, lr, batch_size, nsteps_update, max_ep
          bf16_shadow=True, momentum_correction=False, k_cap_factor=None, overlap=True, dump_grad_every=None,
          metrics_dir=None, f32_matmul=None, train_samples=None, checkpoint_every=2, save_final=False,
          hip_graph=False, selection_quality_every=None, optimizer="sgd", betas=(0.9, 0.999), adam_eps=1e-8,
-         weight_decay=None):
+         weight_decay=None, trust_ratio=False, trust_clip=None):
     rank = hvd.rank()
     device = "cpu"
     if torch.cuda.is_available():
@@ -71,7 +72,8 @@ def ssgd(dnn, dataset, data_dir, nworkers, lr, batch_size, nsteps_update, max_ep
                         pretrain=pretrain, num_steps=num_steps, device=device, amp=amp,
                         channels_last=channels_last, seed=rank, weights_dir=os.path.join(saved_dir, "weights"),
                         train_samples=train_samples, checkpoint_every=checkpoint_every, optimizer=optimizer,
-                        betas=betas, adam_eps=adam_eps, weight_decay=weight_decay)
+                        betas=betas, adam_eps=adam_eps, weight_decay=weight_decay, trust_ratio=trust_ratio,
+                        trust_clip=trust_clip)
     init = torch.tensor([trainer.get_train_epoch(), trainer.get_train_iter()], dtype=torch.int64,
                         device=trainer.device)
     init = hvd.broadcast(init, root_rank=0)
@@ -236,10 +238,26 @@ def _add_optimizer_flags(p):
     p.add_argument("--adam-eps", type=float, default=1e-8)
     p.add_argument("--weight-decay", type=float, default=None,
                    help="weight decay of the decaying group (default: the per-dataset value; AdamW: decoupled)")
+    p.add_argument("--trust-ratio", action="store_true",
+                   help="with --optimizer adamw: LAMB, the AdamW direction scaled per tensor by ||w|| / ||u|| "
+                        "(not for the 1-D / bn / bias group), run as the fused arena update")
+    p.add_argument("--trust-clip", type=float, default=None, help="upper bound of the trust ratio (default: none)")
+
+
+class OptimizerArgumentParser(argparse.ArgumentParser):
+    """Rejects optimizer flag combinations that no optimizer takes (both entry points)."""
+
+    def parse_args(self, args=None, namespace=None):
+        ns = super().parse_args(args, namespace)
+        if ns.trust_ratio and ns.optimizer != "adamw":
+            self.error("--trust-ratio needs --optimizer adamw (LAMB is AdamW plus trust ratios), not %s" % ns.optimizer)
+        if ns.trust_clip is not None and not ns.trust_ratio:
+            self.error("--trust-clip needs --trust-ratio (with --optimizer adamw)")
+        return ns
 
 
 def build_parser():
-    p = argparse.ArgumentParser(description="AllReduce trainer")
+    p = OptimizerArgumentParser(description="AllReduce trainer")
     p.add_argument("--batch-size", type=int, default=32)
     p.add_argument("--nsteps-update", type=int, default=1)
     p.add_argument("--nworkers", type=int, default=None, help="defaults to the launched world size")
@@ -334,7 +352,8 @@ def main(argv=None):
                 metrics_dir=relative_path, f32_matmul=args.f32_matmul, train_samples=args.train_samples,
                 checkpoint_every=args.checkpoint_every, save_final=args.save_final, hip_graph=args.hip_graph,
                 selection_quality_every=args.selection_quality_every, optimizer=args.optimizer,
-                betas=(args.adam_beta1, args.adam_beta2), adam_eps=args.adam_eps, weight_decay=args.weight_decay)
+                betas=(args.adam_beta1, args.adam_beta2), adam_eps=args.adam_eps, weight_decay=args.weight_decay,
+                trust_ratio=args.trust_ratio, trust_clip=args.trust_clip)
 
 
 if __name__ == "__main__":

@@ -12,7 +12,8 @@ MI355X: the update is the fused one-launch SGD over the flat parameter arena
 (the ``DistributedOptimizer`` in a world of one: no hooks, no exchange) and,
 on the GPU, the convolution / linear weight gradients go straight into that
 arena; ``--plain-sgd`` keeps ``torch.optim.SGD`` as the reference did;
-``--optimizer adam|adamw`` runs the fused Adam / AdamW arena update instead.
+``--optimizer adam|adamw`` runs the fused Adam / AdamW arena update instead,
+``--optimizer adamw --trust-ratio`` the fused LAMB one.
 Run: ``python -m gaussiank_sgd_amd.train.single --dnn resnet20 --dataset
 cifar10`` (or ``python -m gaussiank_sgd_amd.train.trainer``).
 """
@@ -34,7 +35,7 @@ from .trainer import DLTrainer, _support_datasets, _support_dnns
 def train_with_single(dnn, dataset, data_dir, nworkers, lr, batch_size, nsteps_update, max_epochs, num_steps=1,
                       amp=None, channels_last=False, max_iters=None, train_samples=None, fused=True,
                       f32_matmul=None, saved_dir=".", optimizer="sgd", betas=(0.9, 0.999), adam_eps=1e-8,
-                      weight_decay=None):
+                      weight_decay=None, trust_ratio=False, trust_clip=None):
     device = "cpu"
     if torch.cuda.is_available():
         torch.cuda.set_device(0)
@@ -46,7 +47,8 @@ def train_with_single(dnn, dataset, data_dir, nworkers, lr, batch_size, nsteps_u
                         data_dir=data_dir, dataset=dataset, dnn=dnn, lr=lr, nworkers=nworkers, prefix="singlegpu",
                         num_steps=num_steps, device=device, amp=amp, channels_last=channels_last,
                         weights_dir=os.path.join(saved_dir, "weights"), train_samples=train_samples,
-                        optimizer=optimizer, betas=betas, adam_eps=adam_eps, weight_decay=weight_decay)
+                        optimizer=optimizer, betas=betas, adam_eps=adam_eps, weight_decay=weight_decay,
+                        trust_ratio=trust_ratio, trust_clip=trust_clip)
     if fused:
         from ..compression import compressors
         from ..parallel.distributed_optimizer import DistributedOptimizer
@@ -92,7 +94,8 @@ def train_with_single(dnn, dataset, data_dir, nworkers, lr, batch_size, nsteps_u
 
 
 def build_parser():
-    p = argparse.ArgumentParser(description="Single trainer")
+    from .dist_trainer import OptimizerArgumentParser, _add_optimizer_flags
+    p = OptimizerArgumentParser(description="Single trainer")
     p.add_argument("--batch-size", type=int, default=32)
     p.add_argument("--nsteps-update", type=int, default=1)
     p.add_argument("--dataset", type=str, default="imagenet", choices=_support_datasets,
@@ -113,7 +116,6 @@ def build_parser():
     p.add_argument("--f32-matmul", type=str, default=os.environ.get("GKSGD_F32_MATMUL", "bf16x6"),
                    choices=["native", "bf16x6"], help="fp32 GEMM algorithm (default: %(default)s, as bench.py)")
     p.add_argument("--saved-dir", type=str, default=".")
-    from .dist_trainer import _add_optimizer_flags
     _add_optimizer_flags(p)
     p.add_argument("--logdir-root", type=str, default="./logs")
     return p
@@ -135,7 +137,8 @@ def main(argv=None):
                              max_iters=args.max_iters, train_samples=args.train_samples, fused=not args.plain_sgd,
                              f32_matmul=args.f32_matmul, saved_dir=args.saved_dir, optimizer=args.optimizer,
                              betas=(args.adam_beta1, args.adam_beta2), adam_eps=args.adam_eps,
-                             weight_decay=args.weight_decay)
+                             weight_decay=args.weight_decay, trust_ratio=args.trust_ratio,
+                             trust_clip=args.trust_clip)
 
 
 if __name__ == "__main__":

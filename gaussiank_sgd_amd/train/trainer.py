@@ -31,7 +31,7 @@ from .. import settings
 from ..data import DATASETS, SyntheticData
 from ..models import MaskedLMLoss, create_net, repackage_hidden
 from ..ops import xent
-from ..optim import sgd_param_groups
+from ..optim import LAMB, sgd_param_groups
 from ..settings import logger
 from ..utils import trace
 from . import schedules
@@ -105,7 +105,8 @@ class DLTrainer:
                  amp: Optional[str] = None, channels_last: bool = False, learnable_data: bool = False,
                  seed: int = 0, data_pool: int = 4, weights_dir: str = "./weights", seq_len: Optional[int] = None,
                  train_samples: Optional[int] = None, checkpoint_every: int = 2, optimizer: str = "sgd",
-                 betas=(0.9, 0.999), adam_eps: float = 1e-8, weight_decay: Optional[float] = None):
+                 betas=(0.9, 0.999), adam_eps: float = 1e-8, weight_decay: Optional[float] = None,
+                 trust_ratio: bool = False, trust_clip: Optional[float] = None):
         # data_dir: real datasets (data/real.py: CIFAR-10 binary, MNIST idx, PTB text, .npz / .npy
         # arrays), sharded by (rank, nworkers); absent or unrecognised -> synthetic, shape-exact
         self.size = size
@@ -182,9 +183,17 @@ class DLTrainer:
         self.weight_decay = weight_decay
         # the same decay / no-decay split (1-D, bn, bias) for every optimizer
         groups = sgd_param_groups(self.net, weight_decay)
+        if trust_ratio and optimizer != "adamw":
+            raise ValueError("trust_ratio=True (LAMB) needs optimizer='adamw', not %r" % (optimizer,))
         if optimizer == "sgd":
             self.optimizer = torch.optim.SGD(groups, lr=self.lr, momentum=self.m, weight_decay=weight_decay,
                                              nesterov=False)
+        elif trust_ratio:
+            # LAMB = AdamW plus per-tensor trust ratios; none for the no-decay (1-D / bn / bias) group
+            groups[0]["adapt"] = False
+            groups[1]["adapt"] = True
+            self.optimizer = LAMB(groups, lr=self.lr, betas=(float(betas[0]), float(betas[1])), eps=float(adam_eps),
+                                  weight_decay=weight_decay, trust_clip=trust_clip)
         elif optimizer in ("adam", "adamw"):
             cls = torch.optim.AdamW if optimizer == "adamw" else torch.optim.Adam
             self.optimizer = cls(groups, lr=self.lr, betas=(float(betas[0]), float(betas[1])), eps=float(adam_eps),
