@@ -48,10 +48,11 @@ class BasicBlock(nn.Module):
 
     def forward(self, x):
         x, xs = x if isinstance(x, tuple) else (x, x)   # (main, shortcut) handles, see BNAct twin
-        identity = xs if self.downsample is None else _shortcut(self.downsample, xs, self.bn2)
         y, st = conv_stats(self.conv1, x)   # BN statistics from the conv epilogue when fused
         out = self.bn1(y, stats=st)
         y, st = conv_stats(self.conv2, out)
+        # the shortcut last (see Bottleneck.forward)
+        identity = xs if self.downsample is None else _shortcut(self.downsample, xs, self.bn2)
         return self.bn2(y, identity, stats=st)
 
 
@@ -71,12 +72,15 @@ class Bottleneck(nn.Module):
 
     def forward(self, x):
         x, xs = x if isinstance(x, tuple) else (x, x)   # (main, shortcut) handles, see BNAct twin
-        identity = xs if self.downsample is None else _shortcut(self.downsample, xs, self.bn3)
         y, st = conv_stats(self.conv1, x)   # BN statistics from the conv epilogue when fused
         out = self.bn1(y, stats=st)
         y, st = conv_stats(self.conv2, out)
         out = self.bn2(y, stats=st)
         y, st = conv_stats(self.conv3, out)
+        # the shortcut after the main path's convolutions: its autograd nodes are the
+        # younger ones, so the backward runs the downsample's grad-input BEFORE conv1's,
+        # which can then add it in its BN-backward epilogue (ops/bn.py BnLink.dy2c)
+        identity = xs if self.downsample is None else _shortcut(self.downsample, xs, self.bn3)
         return self.bn3(y, identity, stats=st)
 
 
@@ -104,6 +108,14 @@ def _shortcut(ds: nn.Module, xs: torch.Tensor, consumer: BNAct) -> torch.Tensor:
     if isinstance(ds, ConvBN):
         return ds.forward_deferred(xs, consumer)
     return ds(xs)
+
+
+def _compact_shortcut(b: nn.Module) -> bool:
+    """A bottleneck whose shortcut is ConvBN(1x1 stride 2): its input's two consumers
+    are conv1 (1x1 stride 1) and that downsample conv (ops/conv1x1.py _dgrad_ds)."""
+    ds = b.downsample
+    return isinstance(b, Bottleneck) and isinstance(ds, ConvBN) and isinstance(ds[0], Conv1x1) and \
+        ds[0].stride == (2, 2)
 
 
 class ResNet(nn.Module):
@@ -145,13 +157,14 @@ class ResNet(nn.Module):
         # ReLU-masked gradient and the BN's reduction partials.  Inside a block
         # that is bn1 -> conv2 (and bn2 -> conv3); a block output feeds the next
         # block's conv1 and, through the shortcut, the next block's last BN, which
-        # hands its residual gradient over -- not a downsample conv, whose
-        # gradient would only arrive after conv1's backward.
+        # hands its residual gradient over -- or, in front of a stride-2 transition
+        # bottleneck, the 1x1 stride-2 downsample conv, which hands over its compact
+        # grad-input (the forward issues the shortcut last, so it is there in time).
         for i, b in enumerate(blocks):
             b.bn1.bwd_link = True
             if isinstance(b, Bottleneck):
                 b.bn2.bwd_link = True
-            if i + 1 < len(blocks) and blocks[i + 1].downsample is None:
+            if i + 1 < len(blocks) and (blocks[i + 1].downsample is None or _compact_shortcut(blocks[i + 1])):
                 (b.bn3 if isinstance(b, Bottleneck) else b.bn2).bwd_link = True
         if zero_init_residual:
             for m in self.modules():

@@ -135,6 +135,11 @@ def splitk_cfgs(dt: torch.dtype, M: int, N: int, K: int) -> List[int]:
     return [c + 10000 * S for S in (2, 4, 8) if K % (64 * S) == 0 and K // S >= 128 for c in base]
 
 
+def nt_x62_cfgs() -> List[int]:
+    """The register-staged bf16x6 row-GEMM configurations alone (fp32, bf16x6 mode)."""
+    return list(_NT_CFGS_X62)
+
+
 # (the implicit-GEMM convolutions split the same way over their (tap, channel)
 # K slices: conv_nt with cfg + 10000 S)
 

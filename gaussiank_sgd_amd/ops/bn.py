@@ -57,20 +57,41 @@ class BnLink:
     block output: next conv1 + shortcut) the shortcut's gradient dy2 must be
     known when the conv1 grad-input runs: the residual consumer (the next
     block's last BN, which runs its backward first) stores it here.
+
+    Transition blocks: the shortcut consumer is a 1x1 stride-2 downsample
+    convolution, whose grad-input touches the even pixels only.  Its backward
+    (issued before conv1's, see models/resnet_imagenet.py) leaves that
+    gradient compact in ``dy2c`` ([N * OH * OW, C] rows, ``geo`` = (H, W, OH,
+    OW)) and returns None to autograd; conv1's grad-input epilogue adds it at
+    the even pixels (ops/conv1x1.py ``_dgrad_bn_ds``).  When conv1 cannot
+    fuse, the BN backward scatters it into a full tensor (``scatter_dy2c``)
+    and runs its own reduction.
     """
 
-    __slots__ = ("h", "mask", "twin", "dy2", "dz", "part")
+    __slots__ = ("h", "mask", "twin", "dy2", "dz", "part", "dy2c", "geo")
 
     def __init__(self):
-        self.h = self.mask = self.dy2 = self.dz = self.part = None
+        self.h = self.mask = self.dy2 = self.dz = self.part = self.dy2c = self.geo = None
         self.twin = False
 
     def ready(self) -> bool:
         """Can the consumer's grad-input fuse the BN-backward reduction now?"""
         return self.h is not None and (not self.twin or self.dy2 is not None)
 
+    def scatter_dy2c(self) -> Optional[torch.Tensor]:
+        """The compact shortcut gradient as a full channels-last [N, C, H, W]
+        tensor (zeros at the pixels without a tap), or None when there is none."""
+        if self.dy2c is None:
+            return None
+        H, W, OH, OW = self.geo
+        C = self.dy2c.shape[1]
+        N = self.dy2c.shape[0] // (OH * OW)
+        full = torch.empty((N, C, H, W), dtype=self.dy2c.dtype, device=self.dy2c.device, memory_format=_CL).zero_()
+        full[:, :, ::2, ::2] = self.dy2c.view(N, OH, OW, C).permute(0, 3, 1, 2)
+        return full
+
     def clear(self) -> None:
-        self.h = self.mask = self.dy2 = self.dz = self.part = None
+        self.h = self.mask = self.dy2 = self.dz = self.part = self.dy2c = self.geo = None
 
 
 class ProducerLink:
@@ -227,9 +248,11 @@ class _BNActFn(torch.autograd.Function):
             dgamma = g[0] if weight is not None and ctx.needs_input_grad[2] else None
             dbeta = g[1] if ctx.needs_input_grad[3] else None
             return (dx, dres, dgamma, dbeta) + (None,) * 14
+        # a compact downsample gradient the consumer's grad-input did not take
+        d2c = link.scatter_dy2c() if link is not None else None
         if link is not None:
             link.clear()
-        dy, dy2 = _grad_pair(grads, x)
+        dy, dy2 = _grad_pair(tuple(grads) + (d2c,), x)
         if dy is None:
             return (None,) * 18
         C = x.shape[1]

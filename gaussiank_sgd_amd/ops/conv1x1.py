@@ -365,11 +365,83 @@ def _dgrad_bn(dy: torch.Tensor, w: torch.Tensor, x_shape, s: int, link, lz=None,
     return dz
 
 
+def _link_on(ds: bool = False) -> bool:
+    """BN-backward fusion switches: GKSGD_BN_LINK=0 turns every linked grad-input
+    off, GKSGD_BN_LINK_DS=0 only the transition blocks' compact shortcut gradient."""
+    return os.environ.get("GKSGD_BN_LINK", "1") != "0" and \
+        not (ds and os.environ.get("GKSGD_BN_LINK_DS", "1") == "0")
+
+
+def _ds_compact_ok(ds_link, x: torch.Tensor, w: torch.Tensor, s: int, dt: torch.dtype) -> bool:
+    """Leave this convolution's grad-input compact on ``ds_link``?  The 1x1
+    stride-2 downsample over the shortcut handle of a linked twin BN output, on
+    the fp32 path whose conv1 grad-input can take it (_ds_fusable): bf16 and the
+    native fp32 mode keep the full-resolution conv_dgrad_s2."""
+    return (ds_link is not None and s == 2 and w.shape[2] == 1 and dt == torch.float32 and _link_on(ds=True) and
+            f32_matmul() == "bf16x6" and ds_link.h is not None and ds_link.h.dtype == dt and
+            ds_link.h.shape == x.shape and ds_link.dy2 is None and ds_link.dy2c is None and
+            x.numel() // x.shape[1] < (1 << 31))
+
+
+def _dgrad_ds(dy: torch.Tensor, w: torch.Tensor, x_shape, wp: bool = False) -> torch.Tensor:
+    """Compact grad-input of a 1x1 stride-2 convolution: only the pixels
+    (2 oh, 2 ow) of the input receive a tap, so dX at those pixels is the plain
+    row GEMM dxc[N * OH * OW, C] = dY rows . W -- a quarter of the rows of the
+    full-resolution gradient, none of its zeros."""
+    N, C, H, W, K, k, p, OH, OW = _geom(x_shape, w, 2)
+    g = _g()
+    dt = dy.dtype
+    dxc = torch.empty(N * OH * OW, C, dtype=dt, device=dy.device)
+    DY = _rows(dy)
+    Wt = _lazy(lambda: weight_prep.transposed_1x1(w, wp))
+    run = lambda c, mb: g.gemm_nt(DY, Wt(), dxc, c, mb)  # noqa: E731
+    cands = autotune.hip_cands(run, product(autotune.nt_cfgs(dt), autotune.NT_GRIDS))
+    cands += autotune.hip_cands(run, product(autotune.splitk_cfgs(dt, N * OH * OW, C, K), autotune.SPLITK_GRIDS))
+    ch = autotune.pick(("dgrad_ds", N, C, H, W, K) + autotune.dkey(dt), cands)
+    run(ch[1], ch[2])
+    return dxc
+
+
+def _ds_fusable(link, x: torch.Tensor, w: torch.Tensor, s: int, dt: torch.dtype, dgrad_key: tuple, lz) -> bool:
+    """Can this grad-input add the compact shortcut gradient of ``link`` in its
+    BN-backward epilogue (_dgrad_bn_ds)?  The fp32 1x1 stride-1 row GEMM on the
+    register-staged bf16x6 kernels, under the rule of _bn_fusable."""
+    if not (s == 1 and w.shape[2] == 1 and dt == torch.float32 and lz is None and _link_on(ds=True) and
+            f32_matmul() == "bf16x6" and link.h is not None and link.h.dtype == dt and link.h.shape == x.shape):
+        return False
+    ch = autotune.choice(dgrad_key)
+    return ch is None or ch[0] == "hip"
+
+
+def _dgrad_bn_ds(dy: torch.Tensor, w: torch.Tensor, x_shape, link, wp: bool = False) -> torch.Tensor:
+    """_dgrad_bn for the conv1 of a transition block: the shortcut gradient is
+    the compact ``link.dy2c`` of the 1x1 stride-2 downsample (_dgrad_ds), added
+    at the even pixels by the epilogue of gemm_nt_x62_kernel -- the only family
+    that reads it, so only its configurations are candidates."""
+    N, C, H, W, K, k, p, OH, OW = _geom(x_shape, w, 1)
+    g = _g()
+    M = N * H * W
+    dt = dy.dtype
+    dz = torch.empty(x_shape, dtype=dt, device=dy.device, memory_format=_CL)
+    st = torch.empty(2, min(1280, (M + 63) // 64), C, dtype=torch.float32, device=dy.device)
+    DY, DZ, H2 = _rows(dy), _rows(dz), _rows(link.h)
+    D2, geo, mask = link.dy2c, list(link.geo), link.mask
+    Wt = _lazy(lambda: weight_prep.transposed_1x1(w, wp))
+    run = lambda c, mb: g.gemm_nt(DY, Wt(), DZ, c, mb, st, None, H2, D2, mask, bn_dy2_geo=geo)  # noqa: E731
+    cands = autotune.hip_cands(run, product(autotune.nt_x62_cfgs(), autotune.NT_GRIDS))
+    ch = autotune.pick(("dgrad_bn_ds", N, C, H, W, K) + autotune.dkey(dt), cands)
+    rows = run(ch[1], ch[2])
+    link.part = (st, int(rows))
+    link.dz = dz
+    link.dy2c = None
+    return dz
+
+
 def _bn_fusable(link, s: int, dgrad_key: tuple) -> bool:
     """Fuse the producing BN's backward reduction into this grad-input?  Only
     when its inputs are ready and the tuned plain grad-input is the HIP kernel
     (a MIOpen choice means the HIP GEMM is the slower one for this shape)."""
-    if link is None or s != 1 or os.environ.get("GKSGD_BN_LINK", "1") == "0" or not link.ready():
+    if link is None or s != 1 or not _link_on() or not link.ready():
         return False
     if link.h.dtype != dgrad_key_dtype(dgrad_key):
         return False
@@ -465,7 +537,7 @@ class _FastConvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, param, w_bf16, sink, stride, stats_box=None, bias=None, bias_sink=None, link=None,
-                dt=torch.bfloat16, plink=None):
+                dt=torch.bfloat16, plink=None, ds_link=None):
         if x.dtype != dt:
             x = x.to(dt)
         x = x.contiguous(memory_format=_CL)
@@ -487,6 +559,7 @@ class _FastConvFn(torch.autograd.Function):
         ctx.stride = stride
         ctx.param_dtype = param.dtype
         ctx.link = link
+        ctx.ds_link = ds_link   # x is the shortcut handle of a linked twin BN output (1x1 stride-2 downsample)
         ctx.dt = dt
         ctx.plink = plink       # the consuming BN may hand back a lazy dz (ops/bn.py ProducerLink)
         ctx.save_for_backward(x, w)
@@ -498,6 +571,7 @@ class _FastConvFn(torch.autograd.Function):
         s = ctx.stride
         dy = dy.to(ctx.dt).contiguous(memory_format=_CL)
         link, ctx.link = ctx.link, None
+        ds_link, ctx.ds_link = ctx.ds_link, None
         plink, ctx.plink = ctx.plink, None
         # lazy BN backward: dy is the consuming BN's dz; dx is formed inside the GEMMs
         lz = plink.lazy if plink is not None and plink.matches(dy) else None
@@ -542,7 +616,17 @@ class _FastConvFn(torch.autograd.Function):
             key = _dgrad_key(N, C, H, W, w.shape[0], w.shape[2], s, ctx.dt)
             prep, ctx.prep = ctx.prep, None
             with weight_prep.use(prep):      # the step scope of the forward (autograd thread)
-                if _bn_fusable(link, s, key):
+                if lz is None and _ds_compact_ok(ds_link, x, w, s, ctx.dt):
+                    # the producing BN's consumers take it from the link: conv1's grad-input
+                    # epilogue, or the BN backward itself; autograd gets no gradient for x
+                    ds_link.dy2c = _dgrad_ds(dy, w, x.shape, wp=ctx.wp)
+                    ds_link.geo = (H, W, dy.shape[2], dy.shape[3])
+                elif link is not None and link.dy2c is not None:
+                    if _ds_fusable(link, x, w, s, ctx.dt, key, lz):
+                        dx = _dgrad_bn_ds(dy, w, x.shape, link, wp=ctx.wp)
+                    else:
+                        dx = _dgrad(dy, w, x.shape, s, lz, plink, wp=ctx.wp)   # the BN backward scatters dy2c
+                elif _bn_fusable(link, s, key):
                     dx = _dgrad_bn(dy, w, x.shape, s, link, lz, plink, wp=ctx.wp)
                 else:
                     dx = _dgrad(dy, w, x.shape, s, lz, plink, wp=ctx.wp)
@@ -587,7 +671,7 @@ class _FastConvFn(torch.autograd.Function):
                 gbias = db
         if plink is not None:
             plink.clear()
-        return dx, gparam, None, None, None, None, gbias, None, None, None, None
+        return dx, gparam, None, None, None, None, gbias, None, None, None, None, None
 
 
 class FastConv2d(nn.Conv2d):
@@ -629,12 +713,13 @@ class FastConv2d(nn.Conv2d):
             if not torch.is_grad_enabled() or self.bias is None or not self.bias.requires_grad:
                 bsink = None
             link = getattr(x, "_gk_bn_link", None)
+            ds_link = getattr(x, "_gk_res_link", None) if f32 and not bf16 and torch.is_grad_enabled() else None
             plink = None
             if f32 and not bf16 and torch.is_grad_enabled():
                 from .bn import ProducerLink
                 plink = ProducerLink()
             y = _FastConvFn.apply(x, self.weight, w_bf16, sink, self.stride[0], box, self.bias, bsink, link,
-                                  torch.bfloat16 if bf16 else torch.float32, plink)
+                                  torch.bfloat16 if bf16 else torch.float32, plink, ds_link)
             if plink is not None:
                 y._gk_plink = plink
             return y

@@ -1257,8 +1257,13 @@ const float* bias_ptr(const c10::optional<at::Tensor>& b, int64_t N) {
 // BatchNorm-backward epilogue operands (gemm.hip BnBwd): all-or-nothing on h
 bool bn_bwd_args(const c10::optional<at::Tensor>& h, const c10::optional<at::Tensor>& dy2,
                  const c10::optional<at::Tensor>& mask, int64_t M, int64_t N,
-                 int64_t ldc, bool has_stats, at::ScalarType dt, gk::BnBwdArgs* out) {
-  if (!h.has_value() || !h->defined()) return false;
+                 int64_t ldc, bool has_stats, at::ScalarType dt, gk::BnBwdArgs* out,
+                 c10::OptionalArrayRef<int64_t> dy2_geo = c10::nullopt) {
+  const bool compact = dy2_geo.has_value();
+  if (!h.has_value() || !h->defined()) {
+    TORCH_CHECK(!compact, "bn_dy2_geo needs the BN-backward epilogue operands");
+    return false;
+  }
   TORCH_CHECK(has_stats, "BN-backward epilogue needs the stats partials buffer");
   auto rows_ok = [&](const at::Tensor& t, const char* what) {
     TORCH_CHECK(t.is_cuda() && t.scalar_type() == dt && t.numel() == M * N &&
@@ -1269,7 +1274,20 @@ bool bn_bwd_args(const c10::optional<at::Tensor>& h, const c10::optional<at::Ten
   rows_ok(*h, "bn h");
   out->h = h->data_ptr();
   out->dy2 = nullptr;
-  if (dy2.has_value() && dy2->defined()) {
+  out->H = out->W = out->OH = out->OW = 0;
+  if (compact) {
+    // compact dy2 (gk_kernels.h BnBwdArgs): [M / (H W) * OH * OW, N] rows, the even pixels of the H x W grid
+    TORCH_CHECK(dy2_geo->size() == 4 && dy2.has_value() && dy2->defined(), "bn_dy2_geo is [H, W, OH, OW] of a given bn_dy2");
+    const int64_t H = (*dy2_geo)[0], W = (*dy2_geo)[1], OH = (*dy2_geo)[2], OW = (*dy2_geo)[3];
+    TORCH_CHECK(H > 0 && W > 0 && OH == (H + 1) / 2 && OW == (W + 1) / 2 && M % (H * W) == 0 && M < (int64_t(1) << 31),
+                "bn_dy2_geo: OH x OW must be the stride-2 grid of the H x W pixels of C's rows (M < 2^31)");
+    TORCH_CHECK(dt == at::kFloat && dy2->is_cuda() && dy2->scalar_type() == dt && dy2->dim() == 2 &&
+                    dy2->size(0) == M / (H * W) * OH * OW && dy2->size(1) == N && dy2->stride(0) == ldc &&
+                    dy2->stride(1) == 1,
+                "compact bn dy2 must be fp32 [M / (H W) * OH * OW, N] with C's row stride");
+    out->dy2 = dy2->data_ptr();
+    out->H = (int)H, out->W = (int)W, out->OH = (int)OH, out->OW = (int)OW;
+  } else if (dy2.has_value() && dy2->defined()) {
     rows_ok(*dy2, "bn dy2");
     out->dy2 = dy2->data_ptr();
   }
@@ -1334,6 +1352,8 @@ struct NtWordAux {
   static int64_t checked(const char* op, int r) {
     TORCH_CHECK(r != gk::cfg::kRowGemmsOnly, op,
                 ": the register-staged bf16x6 kernels (cfg digit 200000/300000) take plain row GEMMs only");
+    TORCH_CHECK(r != gk::cfg::kCompactDy2, op,
+                ": a compact bn_dy2 takes one register-staged bf16x6 row GEMM (cfg digit 200000/300000, no split-K)");
     TORCH_CHECK(r >= 0, op, ": the lazy operand's coefficient table does not fit this tile configuration");
     return r;
   }
@@ -1342,7 +1362,8 @@ struct NtWordAux {
 int64_t gemm_nt(at::Tensor A, at::Tensor B, at::Tensor C, int64_t cfg, int64_t max_blocks,
                 c10::optional<at::Tensor> stats, c10::optional<at::Tensor> bias, c10::optional<at::Tensor> bn_h,
                 c10::optional<at::Tensor> bn_dy2, c10::optional<at::Tensor> bn_mask, c10::optional<at::Tensor> lz_x, c10::optional<at::Tensor> lz_coef,
-                c10::optional<at::Tensor> lz_padz, c10::optional<at::Tensor> lz_padx) {
+                c10::optional<at::Tensor> lz_padz, c10::optional<at::Tensor> lz_padx,
+                c10::OptionalArrayRef<int64_t> bn_dy2_geo) {
   check_rows(A, "A", A);
   check_rows(B, "B", A);
   check_rows(C, "C", A);
@@ -1353,7 +1374,8 @@ int64_t gemm_nt(at::Tensor A, at::Tensor B, at::Tensor C, int64_t cfg, int64_t m
   int rows = 0;
   float* sp = stats_ptr(stats, N, &rows);
   gk::BnBwdArgs bn{};
-  const bool has_bn = bn_bwd_args(bn_h, bn_dy2, bn_mask, M, N, C.stride(0), sp != nullptr, C.scalar_type(), &bn);
+  const bool has_bn = bn_bwd_args(bn_h, bn_dy2, bn_mask, M, N, C.stride(0), sp != nullptr, C.scalar_type(), &bn,
+                                  bn_dy2_geo);
   TORCH_CHECK(!has_bn || !bias.has_value() || !bias->defined(), "gemm_nt: bias and BN epilogue are exclusive");
   gk::LazyArgs lz{};
   const bool has_lz = lazy_args(lz_x, lz_coef, lz_padz, lz_padx, A, K, &lz);
@@ -2241,7 +2263,8 @@ TORCH_LIBRARY(gksgd, m) {
   m.def("cast_bf16(Tensor(a!) dst, Tensor src) -> ()");
   m.def("gemm_supported(int N, int K) -> bool", &gemm_supported);
   m.def("gemm_nt(Tensor A, Tensor B, Tensor(a!) C, int cfg=0, int max_blocks=0, Tensor(b!)? stats=None, "
-        "Tensor? bias=None, Tensor? bn_h=None, Tensor? bn_dy2=None, Tensor? bn_mask=None, Tensor? lz_x=None, Tensor? lz_coef=None, Tensor? lz_padz=None, Tensor? lz_padx=None) -> int");
+        "Tensor? bias=None, Tensor? bn_h=None, Tensor? bn_dy2=None, Tensor? bn_mask=None, Tensor? lz_x=None, Tensor? lz_coef=None, Tensor? lz_padz=None, Tensor? lz_padx=None, "
+        "int[]? bn_dy2_geo=None) -> int");
   m.def("gemm_tn_acc(Tensor G, Tensor X, Tensor(a!) W, int cfg=0, int splits=0, Tensor? lz_x=None, Tensor? lz_coef=None, Tensor? lz_padz=None, Tensor? lz_padx=None) -> ()");
   m.def("conv_nt(Tensor x, Tensor w, Tensor(a!) y, Tensor zero, int stride, int pad, int cfg=0, int max_blocks=0, "
         "Tensor(b!)? stats=None, Tensor? bias=None, Tensor? bn_h=None, Tensor? bn_dy2=None, Tensor? bn_mask=None, "

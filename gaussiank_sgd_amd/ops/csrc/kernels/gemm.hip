@@ -178,6 +178,8 @@ static int nt_run(bool f32, bool gather, const void* A, int64_t lda, const void*
   const cfg::NtPlan p = cfg::nt_plan(w, f32, gather, lazy != nullptr, g.b3 != nullptr, g.RH != 0, splitk_ws != nullptr, K,
                                      g.C, x_elems);
   if (p.status < 0) return p.status;
+  // a compact dy2 is read by gemm_nt_x62_kernel's epilogue only
+  if (bn && bn->OW > 0 && (gather || p.unit != cfg::Unit::x62 || p.planes > 1)) return cfg::kCompactDy2;
   if (p.planes > 1) {
     ConvGeo gz = g;
     gz.bias = nullptr;
@@ -188,7 +190,12 @@ static int nt_run(bool f32, bool gather, const void* A, int64_t lda, const void*
     if (r < 0) return r;
     return splitk_reduce(splitk_ws, p.planes, M, N, static_cast<float*>(C), ldc, g.bias, stats, stats_rows, bn, stream);
   }
-  const BnBwd bb = bn ? BnBwd{bn->h, bn->dy2, bn->mask} : BnBwd{};
+  BnBwd bb = bn ? BnBwd{bn->h, bn->dy2, bn->mask, bn->H, bn->W, bn->OH, bn->OW} : BnBwd{};
+  if (bb.OW > 0) {
+    if (M >= ((int64_t)1 << 31) || M % ((int64_t)bb.H * bb.W) != 0) return cfg::kCompactDy2;
+    magic_u32((uint32_t)(bb.H * bb.W), &bb.mg_hw, &bb.sh_hw);
+    magic_u32((uint32_t)bb.W, &bb.mg_w, &bb.sh_w);
+  }
   return nt_unit(p.unit, gather, A, lda, B, ldb, C, ldc, M, N, K, w, max_blocks, g, stats, (int64_t)stats_rows * N,
                  stats_rows, bb, lazy, stream);
 }

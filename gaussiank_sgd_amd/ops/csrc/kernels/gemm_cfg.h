@@ -60,6 +60,8 @@ enum Status : int {
   kDoesNotFit = -1,    // lazy coefficient table too large for the tile's LDS, or a
                        // split-K request whose preconditions do not hold
   kRowGemmsOnly = -2,  // register-staged bf16x6 kernels asked for a form they do not take
+  kCompactDy2 = -3,    // BN-backward epilogue with a compact dy2 (gk_kernels.h BnBwdArgs) on a
+                       // call that is not one register-staged bf16x6 row GEMM
 };
 
 inline int family_of(int cfg) {

@@ -38,7 +38,8 @@ struct X62Cfg {
   static_assert(LDS <= 160 * 1024, "LDS");
 };
 
-template <int WM, int WN, bool BNB, int NPF = 1, bool GATHER = false, bool P3 = false>
+// D2C (with BNB, row GEMMs): the BN-backward epilogue's dy2 is compact (BnBwd OW > 0)
+template <int WM, int WN, bool BNB, int NPF = 1, bool GATHER = false, bool P3 = false, bool D2C = false>
 __global__ void __launch_bounds__(64 * WM * WN) __attribute__((amdgpu_waves_per_eu(1)))
 gemm_nt_x62_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ B, int64_t ldb,
                    float* __restrict__ C, int64_t ldc, int64_t M, int K, const float* __restrict__ bias,
@@ -252,11 +253,28 @@ gemm_nt_x62_kernel(const float* __restrict__ A, int64_t lda, const float* __rest
           ebits[e] = 0u;
         }
         if (live) {
+          // compact dy2: output row m = (img, ph, pw) of the H x W grid adds dy2's row of
+          // pixel (img, ph / 2, pw / 2) of the OH x OW grid when ph and pw are even, nothing
+          // (-1) otherwise: two multiply-high divisions (the divisors' magic numbers come
+          // with bb; M < 2^31, gemm.hip), written where the loads are so that nothing of
+          // it stays live beside the accumulators (hoisted, the 8-wave tiles spilled more)
+          int32_t d2row = -1;
+          if constexpr (BNB && D2C) {
+            const uint32_t mu = (uint32_t)m;
+            const uint32_t img = (__umulhi(mu, bb.mg_hw) + mu) >> bb.sh_hw, rem = mu - img * (uint32_t)(bb.H * bb.W);
+            const uint32_t ph = (__umulhi(rem, bb.mg_w) + rem) >> bb.sh_w, pw = rem - ph * (uint32_t)bb.W;
+            if (((ph | pw) & 1u) == 0u) d2row = (int32_t)((img * (uint32_t)bb.OH + (ph >> 1)) * (uint32_t)bb.OW + (pw >> 1));
+          }
 #pragma unroll
           for (int e = 0; e < EH; ++e) {
             const int n = n0 + wn * 64 + (nh + e) * 16 + fq * 4;
             ehv[e] = *reinterpret_cast<const f32x4*>(static_cast<const float*>(bb.h) + m * ldc + n);
-            if (bb.dy2) ed2[e] = *reinterpret_cast<const f32x4*>(static_cast<const float*>(bb.dy2) + m * ldc + n);
+            if constexpr (D2C) {
+              if (d2row >= 0)
+                ed2[e] = *reinterpret_cast<const f32x4*>(static_cast<const float*>(bb.dy2) + (int64_t)d2row * ldc + n);
+            } else {
+              if (bb.dy2) ed2[e] = *reinterpret_cast<const f32x4*>(static_cast<const float*>(bb.dy2) + m * ldc + n);
+            }
             ebits[e] = bb.mask ? (uint32_t)bb.mask[m * (Ntot >> 2) + (n >> 2)] : 0xfu;
           }
         }
@@ -398,7 +416,7 @@ gemm_nt_x62_kernel(const float* __restrict__ A, int64_t lda, const float* __rest
   }
 }
 
-template <int WM, int WN, bool BNB, int NPF, bool GATHER, bool P3 = false>
+template <int WM, int WN, bool BNB, int NPF, bool GATHER, bool P3 = false, bool D2C = false>
 int launch_nt_x62(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M, int N,
                   int K, int max_blocks, const float* bias, float* stats, int64_t stats_ld, int stats_rows,
                   const BnBwd& bb, const ConvGeo& geo, hipStream_t stream) {
@@ -412,11 +430,11 @@ int launch_nt_x62(const float* A, int64_t lda, const float* B, int64_t ldb, floa
   if (gx > mtiles) gx = mtiles;
   if (stats && gx > stats_rows) gx = stats_rows;   // one partial row per block
   static bool attr = [] {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_x62_kernel<WM, WN, BNB, NPF, GATHER, P3>),
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_x62_kernel<WM, WN, BNB, NPF, GATHER, P3, D2C>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
   }();
   (void)attr;
-  hipLaunchKernelGGL((gemm_nt_x62_kernel<WM, WN, BNB, NPF, GATHER, P3>), dim3((unsigned)gx, (unsigned)ntiles), dim3(Cfg::THREADS),
+  hipLaunchKernelGGL((gemm_nt_x62_kernel<WM, WN, BNB, NPF, GATHER, P3, D2C>), dim3((unsigned)gx, (unsigned)ntiles), dim3(Cfg::THREADS),
                      Cfg::LDS, stream, A, lda, B, ldb, C, ldc, M, K, bias, stats, stats_ld, bb, geo);
   return (int)gx;
 }
@@ -428,11 +446,16 @@ int nt_x62_dispatch(const float* A, int64_t lda, const float* B, int64_t ldb, fl
                     int N, int K, const cfg::NtWord& w, int max_blocks, const float* bias, float* stats,
                     int64_t stats_ld, int stats_rows, const BnBwd& bb, const ConvGeo& geo, hipStream_t stream) {
   const cfg::X62NtSel s = cfg::nt_x62_select(w, N, geo.b3 != nullptr, bb.h != nullptr);
-#define GK_X62N(WM_, WN_, P3_)                                                                                      \
-  return s.bnb ? launch_nt_x62<WM_, WN_, true, 1, GATHER, P3_>(A, lda, B, ldb, C, ldc, M, N, K, max_blocks, bias, stats, \
-                                                               stats_ld, stats_rows, bb, geo, stream)                  \
-               : launch_nt_x62<WM_, WN_, false, 1, GATHER, P3_>(A, lda, B, ldb, C, ldc, M, N, K, max_blocks, bias,     \
-                                                                stats, stats_ld, stats_rows, bb, geo, stream)
+// (D2C: the compact-dy2 epilogue, row GEMMs with the BN-backward epilogue only)
+#define GK_X62L(WM_, WN_, BNB_, P3_, D2C_)                                                                   \
+  launch_nt_x62<WM_, WN_, BNB_, 1, GATHER, P3_, D2C_>(A, lda, B, ldb, C, ldc, M, N, K, max_blocks, bias, stats, \
+                                                      stats_ld, stats_rows, bb, geo, stream)
+#define GK_X62N(WM_, WN_, P3_)                                             \
+  do {                                                                     \
+    if constexpr (!GATHER)                                                 \
+      if (s.bnb && bb.OW > 0) return GK_X62L(WM_, WN_, true, P3_, true);   \
+    return s.bnb ? GK_X62L(WM_, WN_, true, P3_, false) : GK_X62L(WM_, WN_, false, P3_, false); \
+  } while (0)
 #define GK_X62(WM_, WN_)               \
   case cfg::x62_key(WM_, WN_):         \
     if (s.p3) GK_X62N(WM_, WN_, true); \
@@ -448,6 +471,7 @@ int nt_x62_dispatch(const float* A, int64_t lda, const float* B, int64_t ldb, fl
   }
 #undef GK_X62
 #undef GK_X62N
+#undef GK_X62L
   return cfg::kDoesNotFit;   // not reached: nt_x62_select names instantiated tiles only
 }
 

@@ -48,7 +48,22 @@ struct BnBwd {
   const void* dy2;        // optional second gradient [M, N]
   const uint8_t* mask;    // optional 1-bit ReLU mask, one byte per 16-byte vector: (m, n / V) at
                           // m * (N / V) + n / V, V = 8 (bf16) or 4 (fp32) -- bn_act.hip's layout
+  // OW > 0: dy2 is compact (BnBwdArgs; gemm_nt_x62_kernel only): row m = (n, h, w) of the
+  // H x W grid adds row (n OH + h / 2) OW + w / 2 of dy2 when h and w are even, else 0
+  int H, W, OH, OW;
+  // m / (H W) and m / W for m < 2^31 without a division: (umulhi(m, mg) + m) >> sh (magic_u32)
+  uint32_t mg_hw, sh_hw, mg_w, sh_w;
 };
+
+// Round-up magic number of the divisor d >= 1: (umulhi(n, mg) + n) >> sh == n / d for
+// every n < 2^31 (mg = floor(2^32 (2^sh - d) / d) + 1, sh = ceil(log2 d); umulhi(n, mg) < n,
+// so the sum fits 32 bits)
+inline void magic_u32(uint32_t d, uint32_t* mg, uint32_t* sh) {
+  uint32_t s = 0;
+  while (((uint64_t)1 << s) < d) ++s;
+  *sh = s;
+  *mg = (uint32_t)(((((uint64_t)1 << s) - d) << 32) / d + 1);
+}
 
 // Lazy BatchNorm-backward operand (fp32): the A operand (NT) / G operand (TN)
 // is the gradient of a BN input, dx = k1 ((dz - k2) - (x - mu) k4), which is

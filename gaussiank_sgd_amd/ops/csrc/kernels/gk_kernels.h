@@ -424,10 +424,17 @@ bool gemm_supported(int64_t N, int64_t K);
 // `stats` the per-workgroup partials sum(dz), sum(dz * h) -- feed them to
 // bn_act_backward_pre.  h / dy2 share C's row stride and dtype; mask is the BN
 // forward's 1-bit ReLU mask (bn_act.hip layout).
+// OW > 0: dy2 is compact -- the grad-input of a 1x1 stride-2 convolution over the
+// same H x W input, stored for the pixels that receive a tap only: row
+// (n, oh, ow) of [M / (H W) * OH * OW, N] (C's row stride) is the gradient of
+// pixel (n, 2 oh, 2 ow) and every other pixel gets 0.  fp32 row GEMMs of the
+// register-staged bf16x6 family only (cfg digit 200000 / 300000, no split-K);
+// any other call is refused with cfg::kCompactDy2.
 struct BnBwdArgs {
   const void* h;
   const void* dy2;
   const uint8_t* mask;
+  int H, W, OH, OW;
 };
 // Lazy BN-backward operand (fp32; bn_bwd_finalize_lazy): the A operand of
 // gemm_nt / conv_nt / conv_nt_remap (or G of the grad-weight) is
