@@ -271,6 +271,7 @@ void emb_forward(const int64_t* ids, const int64_t* tt, const float* Ww, const f
                  int64_t M, int T, int H, hipStream_t s) {
   const int H4 = H / 4;
   const int64_t n = M * H4;
+  if (n <= 0) return;   // no tokens: nothing to launch (a zero-sized grid is a launch error)
   hipLaunchKernelGGL(emb_fwd_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, ids, tt, Ww, Wp,
                      Wt, out, M, T, H4);
 }
@@ -280,6 +281,12 @@ void emb_backward(const int64_t* ids, const int64_t* tt, const float* dx, float*
                   int64_t M, int B, int T, int P, int NT, int H, hipStream_t s) {
   (void)ids;
   const int H4 = H / 4;
+  if (M <= 0) {   // no tokens: every gradient row is zero, and no launch may have a zero-sized grid
+    if (dWw) (void)hipMemsetAsync(dWw, 0, sizeof(float) * V * H, s);
+    if (dWp) (void)hipMemsetAsync(dWp, 0, sizeof(float) * P * H, s);
+    if (dWt) (void)hipMemsetAsync(dWt, 0, sizeof(float) * NT * H, s);
+    return;
+  }
   if (dWw && sid) {   // stable-sort buckets + gathers: every row of dWw written (no zero fill)
     int* rstart = wws;
     int* rend = wws + V;

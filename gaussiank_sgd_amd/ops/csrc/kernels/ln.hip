@@ -401,6 +401,7 @@ struct LnBwdLaunch {
 void add_ln_forward(const void* a, const void* x, const float* gamma, const float* beta, void* y, void* hsave,
                     float* mean, float* rstd, int64_t R, int H, float eps, float p, uint32_t seed,
                     const uint32_t* seed_dev, hipStream_t stream, bool f32) {
+  if (R <= 0) return;   // no rows: nothing to launch (a zero-sized grid is a launch error)
   const uint32_t thr = p > 0.f ? (uint32_t)((1.0 - (double)p) * 4294967295.0) : 0u;
   const float scale = p > 0.f ? 1.f / (1.f - p) : 1.f;
   const LnFwdArgs args{a, x, gamma, beta, y, hsave, mean, rstd, R, H, eps, seed, thr, scale, seed_dev, stream, f32};
@@ -410,6 +411,13 @@ void add_ln_forward(const void* a, const void* x, const float* gamma, const floa
 void add_ln_backward(const void* dy, const void* hsave, const float* mean, const float* rstd, const float* gamma,
                      void* dx, void* da, float* dgamma, float* dbeta, int accumulate, float* ws, int64_t R, int H,
                      float p, uint32_t seed, const uint32_t* seed_dev, hipStream_t stream, bool f32) {
+  if (R <= 0) {   // no rows: dx / da are empty and the parameter gradients get zero sums
+    if (!accumulate) {
+      if (dgamma) (void)hipMemsetAsync(dgamma, 0, sizeof(float) * H, stream);
+      if (dbeta) (void)hipMemsetAsync(dbeta, 0, sizeof(float) * H, stream);
+    }
+    return;
+  }
   const uint32_t thr = p > 0.f ? (uint32_t)((1.0 - (double)p) * 4294967295.0) : 0u;
   const float scale = p > 0.f ? 1.f / (1.f - p) : 1.f;
   const int64_t P = (R + kLnRowsPerBlock - 1) / kLnRowsPerBlock;

@@ -103,12 +103,14 @@ bool xent_supported(int V) { return V % 2 == 0 && V >= 2; }
 
 void xent_forward(const void* logits, const int64_t* labels, float* lse, float* loss, int64_t R, int V, int64_t ignore,
                   hipStream_t s) {
+  if (R <= 0) return;   // no rows: nothing to launch (a zero-sized grid is a launch error)
   hipLaunchKernelGGL(xent_fwd_kernel, dim3((unsigned)R), dim3(kBlock), 0, s, (const uint16_t*)logits, labels, lse, loss,
                      V, ignore);
 }
 
 void xent_backward(const void* logits, const int64_t* labels, const float* lse, const float* scale, void* grad,
                    int64_t R, int V, int64_t ignore, hipStream_t s) {
+  if (R <= 0) return;
   hipLaunchKernelGGL(xent_bwd_kernel, dim3((unsigned)R), dim3(kBlock), 0, s, (const uint16_t*)logits, labels, lse,
                      scale, (uint16_t*)grad, V, ignore);
 }

@@ -6,8 +6,10 @@ post-LN transformer sub-layer output (BERT: ``LN(x + drop(attn_out))`` and
 backward (plus a small dgamma / dbeta finalize), with bf16 row tensors under
 autocast and fp32 ones at the reference's precision (``GKSGD_LN_F32=0``
 keeps PyTorch there); the dropout mask is a hash of (seed, row, column),
-regenerated in the backward instead of stored.  Elsewhere (CPU) it is the
-plain PyTorch composition with identical semantics.  ``ln`` is an ordinary
+regenerated in the backward instead of stored.  Elsewhere (CPU, or a row
+length the kernels do not take) it is the plain PyTorch composition with
+identical semantics; bf16 rows through fp32 parameters outside autocast are
+normalised in fp32 and returned in bf16 there, as the kernels do.  ``ln`` is an ordinary
 ``nn.LayerNorm`` (its parameters / state_dict keys are untouched).
 """
 from __future__ import annotations
@@ -105,4 +107,10 @@ def add_layernorm(a: torch.Tensor, x: torch.Tensor, ln: nn.LayerNorm, p: float =
             direct = None
         return _AddLNFn.apply(a, x, ln.weight, ln.bias, ln.eps, p, seed, direct,
                               capture_seed_word(x.device) if p > 0 else None, _compute_dtype(x))
-    return ln(x + F.dropout(a, p, training=p > 0))
+    h = x + F.dropout(a, p, training=p > 0)
+    if ln.elementwise_affine and h.dtype != ln.weight.dtype and not torch.is_autocast_enabled(h.device.type):
+        # bf16 rows through an fp32 LayerNorm outside autocast (a row length the kernels do not take):
+        # PyTorch's GPU layer_norm refuses the mixed dtypes, so normalise at the parameters' precision,
+        # as the kernels do, and keep the rows' dtype
+        return F.layer_norm(h.to(ln.weight.dtype), ln.normalized_shape, ln.weight, ln.bias, ln.eps).to(h.dtype)
+    return ln(h)

@@ -6,7 +6,14 @@ rows).  On the GPU with bf16 logits it is one HIP row pass forward (max,
 sum of exp, the row's log-sum-exp kept) and one backward that writes the bf16
 logit gradient ``(softmax - onehot) / count`` directly -- no fp32 copy of the
 logits, no separate log_softmax / nll / cast kernels.  Elsewhere it is the
-PyTorch call.
+PyTorch call with ``reduction="sum"`` divided by the same count.
+
+One difference from ``F.cross_entropy``: the divisor is ``max(count, 1)``, so
+a batch in which every row is ignored (or an empty one) gives loss 0.0 and an
+all-zero gradient on both paths, where ``F.cross_entropy`` returns NaN.
+``count`` is the number of labels that differ from ``ignore_index``: the
+kernels treat a label outside [0, V) as ignored (no loss, zero gradient), but
+such a row is still counted in the divisor.
 """
 from __future__ import annotations
 
@@ -58,4 +65,6 @@ def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, ignore_index: int 
     V = logits.shape[-1]
     if fused_available(logits):
         return _XentFn.apply(logits.reshape(-1, V).contiguous(), labels.reshape(-1).long().contiguous(), ignore_index)
-    return F.cross_entropy(logits.reshape(-1, V).float(), labels.reshape(-1), ignore_index=ignore_index)
+    labels = labels.reshape(-1)
+    total = F.cross_entropy(logits.reshape(-1, V).float(), labels, ignore_index=ignore_index, reduction="sum")
+    return total / (labels != ignore_index).sum().clamp(min=1)
