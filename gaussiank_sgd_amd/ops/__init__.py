@@ -832,11 +832,31 @@ def make_chunk_table(segments: Sequence[Tuple[int, int, int, int]], device) -> t
     return torch.tensor(words, dtype=torch.int64, device=device)
 
 
-def _decode_chunks(chunks: torch.Tensor):
-    c = chunks.view(-1, 2).cpu()
+def _decode_chunks(chunks: torch.Tensor, check_seg: bool = False):
+    """[(start, len, group, seg)] of a chunk table, decoded on the host.  ``check_seg``: raise on a segment id
+    beyond the table's 15-bit field instead of masking it."""
     out = []
-    for start, w in c.tolist():
-        out.append((start, w & 0xFFFFFFFF, (w >> 32) & 0xFFFF, (w >> 48) & 0x7FFF))
+    for ci, (start, w) in enumerate(chunks.view(-1, 2).cpu().tolist()):
+        seg = (w >> 48) & 0xFFFF
+        if check_seg and seg > 0x7FFF:
+            raise ValueError("chunk %d: segment id %d exceeds the chunk table's 15-bit field" % (ci, seg))
+        out.append((start, w & 0xFFFFFFFF, (w >> 32) & 0xFFFF, seg & 0x7FFF))
+    return out
+
+
+def _hyper_lists(groups: Sequence[dict], *specs) -> List[list]:
+    """One list per spec over the param groups, as the native ops take them.  A spec is a key every group
+    must have or ``(key, default)``; a bool default makes a 0/1 flag, everything else a float.  ``beta1`` /
+    ``beta2`` read ``betas``."""
+    out = []
+    for spec in specs:   # on the host path of every step: one comprehension per list
+        key, default = spec if type(spec) is tuple else (spec, None)
+        if key == "beta1" or key == "beta2":
+            out.append([float(p["betas"][key == "beta2"]) for p in groups])
+        elif type(default) is bool:
+            out.append([int(bool(p.get(key, default))) for p in groups])
+        else:
+            out.append([float(p[key] if default is None else p.get(key, default)) for p in groups])
     return out
 
 
@@ -847,16 +867,15 @@ def momentum_correct_(u: torch.Tensor, g: torch.Tensor, w: torch.Tensor, chunks:
     ``groups``: dicts with ``momentum`` and ``weight_decay`` per param group.
     ``chunk_list``: decoded chunks (CPU path; avoids a device->host copy).
     """
+    mus, wds = _hyper_lists(groups, "momentum", ("weight_decay", 0.0))
     if u.is_cuda:
         require_native(u)
-        _ops().momentum_correct(u, g, w, chunks, int(begin), int(count), [float(p["momentum"]) for p in groups],
-                                [float(p.get("weight_decay", 0.0)) for p in groups])
+        _ops().momentum_correct(u, g, w, chunks, int(begin), int(count), mus, wds)
         return
     cl = chunk_list if chunk_list is not None else _decode_chunks(chunks)
     for start, ln, gi, _ in cl[begin:begin + count]:
-        p = groups[gi]
         us, gs, ws = u[start:start + ln], g[start:start + ln], w[start:start + ln]
-        us.mul_(float(p["momentum"])).add_(gs).add_(ws, alpha=float(p.get("weight_decay", 0.0)))
+        us.mul_(mus[gi]).add_(gs).add_(ws, alpha=wds[gi])
         gs.copy_(us)
 
 
@@ -917,37 +936,42 @@ def fused_sgd_(w: torch.Tensor, m: Optional[torch.Tensor], g: torch.Tensor, chun
     ``lr_mult``: optional fp32 device scalar multiplying every lr, read by the
     kernel (a captured HIP graph follows the host lr schedule through it).
     """
+    hyper = _hyper_lists(groups, "lr", "momentum", ("dampening", 0.0), ("weight_decay", 0.0), ("nesterov", False),
+                         ("first_step", False))
     if w.is_cuda:
         require_native(w)
-        _ops().fused_sgd(w, m, g, chunks, [float(p["lr"]) for p in groups], [float(p["momentum"]) for p in groups],
-                         [float(p.get("dampening", 0.0)) for p in groups],
-                         [float(p.get("weight_decay", 0.0)) for p in groups],
-                         [int(bool(p.get("nesterov", False))) for p in groups],
-                         [int(bool(p.get("first_step", False))) for p in groups], bool(zero_grad), grad_scale,
-                         w_bf16, lr_mult)
+        _ops().fused_sgd(w, m, g, chunks, *hyper, bool(zero_grad), grad_scale, w_bf16, lr_mult)
         return
     gs = float(grad_scale) if grad_scale is not None else 1.0
     lm = float(lr_mult) if lr_mult is not None else 1.0
     for start, ln, gi, _ in _decode_chunks(chunks):
-        p = groups[gi]
+        lr, mom, dampening, wd, nesterov, first_step = (h[gi] for h in hyper)
         ws = w[start:start + ln]
         d = g[start:start + ln] * gs
-        wd = float(p.get("weight_decay", 0.0))
         if wd != 0:
             d = d + wd * ws
-        mom = float(p["momentum"])
         if mom != 0:
             ms = m[start:start + ln]
-            if p.get("first_step", False):
+            if first_step:
                 ms.copy_(d)
             else:
-                ms.mul_(mom).add_(d, alpha=1 - float(p.get("dampening", 0.0)))
-            d = d + mom * ms if p.get("nesterov", False) else ms
-        ws.add_(d, alpha=-float(p["lr"]) * lm)
+                ms.mul_(mom).add_(d, alpha=1 - dampening)
+            d = d + mom * ms if nesterov else ms
+        ws.add_(d, alpha=-lr * lm)
         if w_bf16 is not None:
             w_bf16[start:start + ln].copy_(ws)
         if zero_grad:
             g[start:start + ln].zero_()
+
+
+# The moment update and sqrt(vhat) + eps of the Adam and LAMB fallbacks, in torch's single-tensor forms.
+def _adam_moments_(ms: torch.Tensor, vs: torch.Tensor, d: torch.Tensor, b1: float, b2: float) -> None:
+    ms.lerp_(d, 1.0 - b1)
+    vs.mul_(b2).addcmul_(d, d, value=1.0 - b2)
+
+
+def _adam_denom(vs: torch.Tensor, b2: float, t: float, eps: float) -> torch.Tensor:
+    return (vs.sqrt() / math.sqrt(1.0 - b2 ** t)).add_(eps)
 
 
 def fused_adam_(w: torch.Tensor, m: torch.Tensor, v: torch.Tensor, g: torch.Tensor, chunks: torch.Tensor,
@@ -967,35 +991,28 @@ def fused_adam_(w: torch.Tensor, m: torch.Tensor, v: torch.Tensor, g: torch.Tens
     padding, an element that never saw a gradient) is 0 / (0 + eps) = 0 and
     stays exactly 0; with eps = 0 it would be 0 / 0.
     """
-    if any(not float(p["eps"]) > 0.0 for p in groups):
+    hyper = lrs, b1s, b2s, epss, wds, decoupled = _hyper_lists(groups, "lr", "beta1", "beta2", "eps",
+                                                               ("weight_decay", 0.0), ("decoupled", False))
+    if any(not eps > 0.0 for eps in epss):
         raise ValueError("fused_adam_ needs eps > 0 in every group (eps = 0 turns zero slots into 0 / 0)")
     if w.is_cuda:
         require_native(w)
-        _ops().fused_adam(w, m, v, g, chunks, step, [float(p["lr"]) for p in groups],
-                          [float(p["betas"][0]) for p in groups], [float(p["betas"][1]) for p in groups],
-                          [float(p["eps"]) for p in groups], [float(p.get("weight_decay", 0.0)) for p in groups],
-                          [int(bool(p.get("decoupled", False))) for p in groups], bool(zero_grad), grad_scale,
-                          w_bf16, lr_mult)
+        _ops().fused_adam(w, m, v, g, chunks, step, *hyper, bool(zero_grad), grad_scale, w_bf16, lr_mult)
         return
     step += 1
     t = float(step)
     gs = float(grad_scale) if grad_scale is not None else 1.0
     lm = float(lr_mult) if lr_mult is not None else 1.0
     for start, ln, gi, _ in _decode_chunks(chunks):
-        p = groups[gi]
-        lr = float(p["lr"]) * lm
-        b1, b2 = float(p["betas"][0]), float(p["betas"][1])
-        wd = float(p.get("weight_decay", 0.0))
+        lr, b1, b2, eps, wd = lrs[gi] * lm, b1s[gi], b2s[gi], epss[gi], wds[gi]
         ws, ms, vs = w[start:start + ln], m[start:start + ln], v[start:start + ln]
         d = g[start:start + ln] * gs
-        if p.get("decoupled", False):
+        if decoupled[gi]:
             ws.mul_(1.0 - lr * wd)
         elif wd != 0:
             d = d + wd * ws
-        ms.lerp_(d, 1.0 - b1)
-        vs.mul_(b2).addcmul_(d, d, value=1.0 - b2)
-        denom = (vs.sqrt() / math.sqrt(1.0 - b2 ** t)).add_(float(p["eps"]))
-        ws.addcdiv_(ms, denom, value=-lr / (1.0 - b1 ** t))
+        _adam_moments_(ms, vs, d, b1, b2)
+        ws.addcdiv_(ms, _adam_denom(vs, b2, t, eps), value=-lr / (1.0 - b1 ** t))
         if w_bf16 is not None:
             w_bf16[start:start + ln].copy_(ws)
         if zero_grad:
@@ -1026,27 +1043,18 @@ def make_lamb_workspace(chunks: torch.Tensor, device) -> LambWorkspace:
     precondition for graph capture).  A tensor's chunks must be consecutive in
     the table -- its partial sums are added in table order -- and its id must
     fit the table's 15-bit field."""
-    table = chunks.view(-1, 2).cpu().tolist()
-    decoded = []
-    first: dict = {}
-    count: dict = {}
-    for ci, (start, word) in enumerate(table):
-        seg = (word >> 48) & 0xFFFF
-        if seg > 0x7FFF:
-            raise ValueError("chunk %d: segment id %d exceeds the chunk table's 15-bit field" % (ci, seg))
-        if seg not in first:
-            first[seg], count[seg] = ci, 0
-        elif first[seg] + count[seg] != ci:
+    decoded = _decode_chunks(chunks, check_seg=True)
+    nseg = max((seg for _, _, _, seg in decoded), default=-1) + 1
+    rng = [0] * (2 * nseg)   # first chunk, number of chunks of every tensor
+    for ci, (_, _, _, seg) in enumerate(decoded):
+        if rng[2 * seg + 1] == 0:
+            rng[2 * seg] = ci
+        elif rng[2 * seg] + rng[2 * seg + 1] != ci:
             raise ValueError("segment %d: its chunks are not consecutive in the chunk table (chunk %d follows chunk "
-                             "%d)" % (seg, ci, first[seg] + count[seg] - 1))
-        count[seg] += 1
-        decoded.append((start, word & 0xFFFFFFFF, (word >> 32) & 0xFFFF, seg))
-    nseg = max(first) + 1 if first else 0
-    rng = [0] * (2 * nseg)
-    for seg, f in first.items():
-        rng[2 * seg], rng[2 * seg + 1] = f, count[seg]
+                             "%d)" % (seg, ci, rng[2 * seg] + rng[2 * seg + 1] - 1))
+        rng[2 * seg + 1] += 1
     return LambWorkspace(torch.tensor(rng, dtype=torch.int32, device=device),
-                         torch.zeros(2 * len(table), dtype=torch.float64, device=device),
+                         torch.zeros(2 * len(decoded), dtype=torch.float64, device=device),
                          torch.ones(nseg, dtype=torch.float32, device=device), decoded)
 
 
@@ -1067,7 +1075,9 @@ def fused_lamb_(w: torch.Tensor, m: torch.Tensor, v: torch.Tensor, g: torch.Tens
     reduced in an order that depends on the table alone (no atomics), so
     replicas stay bit-identical.
     """
-    if any(not float(p["eps"]) > 0.0 for p in groups):
+    hyper = lrs, b1s, b2s, epss, wds, adapt = _hyper_lists(groups, "lr", "beta1", "beta2", "eps",
+                                                           ("weight_decay", 0.0), ("adapt", True))
+    if any(not eps > 0.0 for eps in epss):
         raise ValueError("fused_lamb_ needs eps > 0 in every group (eps = 0 turns zero slots into 0 / 0)")
     if ws.nchunks != chunks.numel() // 2:
         raise ValueError("the LAMB workspace was built for a table of %d chunks, not %d" % (ws.nchunks,
@@ -1075,32 +1085,23 @@ def fused_lamb_(w: torch.Tensor, m: torch.Tensor, v: torch.Tensor, g: torch.Tens
     clip = [float(p.get("trust_clip") or 0.0) for p in groups]
     if w.is_cuda:
         require_native(w)
-        _ops().fused_lamb(w, m, v, g, chunks, step, ws.seg_range, ws.part, ws.trust, [float(p["lr"]) for p in groups],
-                          [float(p["betas"][0]) for p in groups], [float(p["betas"][1]) for p in groups],
-                          [float(p["eps"]) for p in groups], [float(p.get("weight_decay", 0.0)) for p in groups],
-                          [int(bool(p.get("adapt", True))) for p in groups], clip, bool(zero_grad), grad_scale,
-                          w_bf16, lr_mult)
+        _ops().fused_lamb(w, m, v, g, chunks, step, ws.seg_range, ws.part, ws.trust, *hyper, clip, bool(zero_grad),
+                          grad_scale, w_bf16, lr_mult)
         return
     step += 1
     t = float(step)
     gs = float(grad_scale) if grad_scale is not None else 1.0
     lm = float(lr_mult) if lr_mult is not None else 1.0
 
-    def direction(start, ln, p):
-        b1, b2 = float(p["betas"][0]), float(p["betas"][1])
-        denom = (v[start:start + ln].sqrt() / math.sqrt(1.0 - b2 ** t)).add_(float(p["eps"]))
-        return (m[start:start + ln] / (1.0 - b1 ** t)).div_(denom).add_(w[start:start + ln],
-                                                                        alpha=float(p.get("weight_decay", 0.0)))
+    def direction(start, ln, gi):
+        denom = _adam_denom(v[start:start + ln], b2s[gi], t, epss[gi])
+        return (m[start:start + ln] / (1.0 - b1s[gi] ** t)).div_(denom).add_(w[start:start + ln], alpha=wds[gi])
 
     sumsq = torch.zeros(2 * ws.nseg, dtype=torch.float64)
     for start, ln, gi, seg in ws.segments:
-        p = groups[gi]
-        b1, b2 = float(p["betas"][0]), float(p["betas"][1])
-        d = g[start:start + ln] * gs
-        m[start:start + ln].lerp_(d, 1.0 - b1)
-        v[start:start + ln].mul_(b2).addcmul_(d, d, value=1.0 - b2)
+        _adam_moments_(m[start:start + ln], v[start:start + ln], g[start:start + ln] * gs, b1s[gi], b2s[gi])
         sumsq[2 * seg] += (w[start:start + ln].double() ** 2).sum()
-        sumsq[2 * seg + 1] += (direction(start, ln, p).double() ** 2).sum()
+        sumsq[2 * seg + 1] += (direction(start, ln, gi).double() ** 2).sum()
     ws.trust.fill_(1.0)
     for seg in range(ws.nseg):
         first, n = int(ws.seg_range[2 * seg]), int(ws.seg_range[2 * seg + 1])
@@ -1108,15 +1109,14 @@ def fused_lamb_(w: torch.Tensor, m: torch.Tensor, v: torch.Tensor, g: torch.Tens
             continue
         gi = ws.segments[first][2]
         wn, un = float(sumsq[2 * seg].sqrt().float()), float(sumsq[2 * seg + 1].sqrt().float())
-        trust = wn / un if groups[gi].get("adapt", True) and wn > 0 and un > 0 else 1.0
+        trust = wn / un if adapt[gi] and wn > 0 and un > 0 else 1.0
         if clip[gi] > 0:
             trust = min(trust, clip[gi])
         ws.trust[seg] = trust
     for start, ln, gi, seg in ws.segments:
-        p = groups[gi]
         ws_ = w[start:start + ln]
-        ws_.add_(direction(start, ln, p), alpha=-float(torch.tensor(float(p["lr"]) * lm * float(ws.trust[seg]),
-                                                                  dtype=torch.float32)))
+        ws_.add_(direction(start, ln, gi), alpha=-float(torch.tensor(lrs[gi] * lm * float(ws.trust[seg]),
+                                                                   dtype=torch.float32)))
         if w_bf16 is not None:
             w_bf16[start:start + ln].copy_(ws_)
         if zero_grad:
@@ -1135,24 +1135,23 @@ def segmented_sumsq_(w: torch.Tensor, g: torch.Tensor, chunks: torch.Tensor, out
 
 def fused_lars_(w: torch.Tensor, m: torch.Tensor, g: torch.Tensor, chunks: torch.Tensor, seg_sumsq: torch.Tensor,
                 groups: Sequence[dict]) -> None:
+    hyper = _hyper_lists(groups, "lr", "momentum", "weight_decay", "eeta", "epsilon")
     if w.is_cuda:
         require_native(w)
-        _ops().fused_lars(w, m, g, chunks, seg_sumsq, [float(p["lr"]) for p in groups],
-                          [float(p["momentum"]) for p in groups], [float(p["weight_decay"]) for p in groups],
-                          [float(p["eeta"]) for p in groups], [float(p["epsilon"]) for p in groups])
+        _ops().fused_lars(w, m, g, chunks, seg_sumsq, *hyper)
         return
     for start, ln, gi, seg in _decode_chunks(chunks):
-        p = groups[gi]
+        lr, mom, wd, eeta, epsilon = (h[gi] for h in hyper)
         wn = float(seg_sumsq[2 * seg]) ** 0.5
         gn = float(seg_sumsq[2 * seg + 1]) ** 0.5
         trust = 1.0
         if wn > 0 and gn > 0:
-            trust = p["eeta"] * wn / (gn + p["weight_decay"] * wn + p["epsilon"])
+            trust = eeta * wn / (gn + wd * wn + epsilon)
         trust = min(max(trust, 0.0), 50.0)
         ws = w[start:start + ln]
-        d = (g[start:start + ln] + p["weight_decay"] * ws).clamp_(-10.0, 10.0)
+        d = (g[start:start + ln] + wd * ws).clamp_(-10.0, 10.0)
         ms = m[start:start + ln]
-        ms.mul_(p["momentum"]).add_(d, alpha=p["lr"] * trust)
+        ms.mul_(mom).add_(d, alpha=lr * trust)
         ws.sub_(ms)
 
 

@@ -231,37 +231,85 @@ void sign_bucket_decompress(at::Tensor x, at::Tensor mask, at::Tensor means) {
 // ---------------------------------------------------------------------------
 // fused optimizers
 // ---------------------------------------------------------------------------
+using OptTensor = c10::optional<at::Tensor>;
+
+bool given(const OptTensor& t) { return t.has_value() && t->defined(); }
+
+bool aligned16(const at::Tensor& t) { return (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0; }
+
+// The arenas of one launch: fp32 contiguous device tensors of one size, 16-byte aligned (a chunk is streamed as
+// float4 from its start).
+struct NamedTensor {
+  const char* name;
+  const at::Tensor& t;
+};
+void check_arenas(std::initializer_list<NamedTensor> arenas, const char* size_msg,
+                  const char* align_msg = "arenas must be 16-byte aligned") {
+  for (const NamedTensor& a : arenas) {
+    check_f32(a.t, a.name);
+    TORCH_CHECK(a.t.numel() == arenas.begin()->t.numel(), size_msg);
+    TORCH_CHECK(aligned16(a.t), align_msg);
+  }
+}
+
+// 1..kMaxGroups param groups, and one entry per group in every hyper-parameter list (the launchers index them by
+// the chunk's group id)
+void check_groups(size_t ng, std::initializer_list<size_t> list_sizes,
+                  const char* msg = "hyper-parameter lists must have one entry per group") {
+  TORCH_CHECK(ng >= 1 && ng <= (size_t)gk::kMaxGroups, "1..8 param groups supported");
+  for (size_t n : list_sizes) TORCH_CHECK(n == ng, msg);
+}
+
 void check_chunks(const at::Tensor& chunks) {
   check_dev(chunks, "chunks");
   TORCH_CHECK(chunks.scalar_type() == at::kLong && chunks.numel() % 2 == 0,
               "chunks must be int64[nchunks*2] (start, len|group<<32|seg<<48)");
 }
 
-void fused_sgd(at::Tensor w, c10::optional<at::Tensor> m, at::Tensor g, at::Tensor chunks, std::vector<double> lr,
-               std::vector<double> momentum, std::vector<double> dampening, std::vector<double> weight_decay,
-               std::vector<int64_t> nesterov, std::vector<int64_t> first_step, bool zero_grad,
-               c10::optional<at::Tensor> grad_scale, c10::optional<at::Tensor> w_bf16,
-               c10::optional<at::Tensor> lr_mult) {
-  check_f32(w, "w");
-  check_f32(g, "g");
+// rows [begin, begin + count) of the chunk table
+template <class Args>
+void set_chunks(Args& a, const at::Tensor& chunks, int64_t begin, int64_t count) {
   check_chunks(chunks);
+  TORCH_CHECK(begin >= 0 && count >= 0 && (begin + count) * 2 <= chunks.numel(), "chunk range out of bounds");
+  a.chunks = reinterpret_cast<const gk::Chunk*>(chunks.data_ptr<int64_t>()) + begin;
+  a.nchunks = (int)count;
+}
+template <class Args>
+void set_chunks(Args& a, const at::Tensor& chunks) {
+  set_chunks(a, chunks, 0, chunks.numel() / 2);
+}
+
+// grad_scale, lr_mult: fp32 device scalars; w_bf16: the bf16 shadow arena of w
+void set_optional(gk::ArenaArgs& a, const at::Tensor& w, const OptTensor& grad_scale, const OptTensor& w_bf16,
+                  const OptTensor& lr_mult) {
+  if (given(grad_scale)) {
+    check_f32(*grad_scale, "grad_scale");
+    a.grad_scale = grad_scale->data_ptr<float>();
+  }
+  if (given(w_bf16)) {
+    TORCH_CHECK(w_bf16->is_cuda() && w_bf16->scalar_type() == at::kBFloat16 && w_bf16->numel() == w.numel() &&
+                    w_bf16->is_contiguous() && aligned16(*w_bf16),
+                "w_bf16 must be a 16-byte aligned contiguous bf16 arena of w's size");
+    a.w_bf16 = reinterpret_cast<uint16_t*>(w_bf16->data_ptr());
+  }
+  if (given(lr_mult)) {
+    check_f32(*lr_mult, "lr_mult");
+    a.lr_mult = lr_mult->data_ptr<float>();
+  }
+}
+
+void fused_sgd(at::Tensor w, OptTensor m, at::Tensor g, at::Tensor chunks, std::vector<double> lr,
+               std::vector<double> momentum, std::vector<double> dampening, std::vector<double> weight_decay,
+               std::vector<int64_t> nesterov, std::vector<int64_t> first_step, bool zero_grad, OptTensor grad_scale,
+               OptTensor w_bf16, OptTensor lr_mult) {
   const size_t ng = lr.size();
-  TORCH_CHECK(ng >= 1 && ng <= (size_t)gk::kMaxGroups, "1..8 param groups supported");
-  TORCH_CHECK(momentum.size() == ng && dampening.size() == ng && weight_decay.size() == ng && nesterov.size() == ng &&
-                  first_step.size() == ng,
-              "hyper-parameter lists must have one entry per group");
-  TORCH_CHECK(w.numel() == g.numel(), "w/g size mismatch");
-  TORCH_CHECK((reinterpret_cast<uintptr_t>(w.data_ptr()) & 15) == 0 &&
-                  (reinterpret_cast<uintptr_t>(g.data_ptr()) & 15) == 0,
-              "arenas must be 16-byte aligned");
+  check_groups(ng, {momentum.size(), dampening.size(), weight_decay.size(), nesterov.size(), first_step.size()});
+  check_arenas({{"w", w}, {"g", g}}, "w/g size mismatch");
   gk::SgdArgs a;
   a.w = w.data_ptr<float>();
   a.g = g.data_ptr<float>();
-  a.m = nullptr;
-  if (m.has_value() && m->defined()) {
-    check_f32(*m, "m");
-    TORCH_CHECK(m->numel() == w.numel(), "momentum arena size mismatch");
-    TORCH_CHECK((reinterpret_cast<uintptr_t>(m->data_ptr()) & 15) == 0, "momentum arena must be 16-byte aligned");
+  if (given(m)) {
+    check_arenas({{"w", w}, {"m", *m}}, "momentum arena size mismatch", "momentum arena must be 16-byte aligned");
     a.m = m->data_ptr<float>();
   }
   for (size_t i = 0; i < ng; ++i) {
@@ -274,85 +322,46 @@ void fused_sgd(at::Tensor w, c10::optional<at::Tensor> m, at::Tensor g, at::Tens
     TORCH_CHECK(a.groups[i].momentum == 0.f || a.m != nullptr, "momentum arena required");
   }
   a.ngroups = (int)ng;
-  a.chunks = reinterpret_cast<const gk::Chunk*>(chunks.data_ptr<int64_t>());
-  a.nchunks = (int)(chunks.numel() / 2);
   a.zero_grad = zero_grad ? 1 : 0;
-  a.grad_scale = nullptr;
-  if (grad_scale.has_value() && grad_scale->defined()) {
-    check_f32(*grad_scale, "grad_scale");
-    a.grad_scale = grad_scale->data_ptr<float>();
-  }
-  if (w_bf16.has_value() && w_bf16->defined()) {
-    TORCH_CHECK(w_bf16->scalar_type() == at::kBFloat16 && w_bf16->numel() == w.numel() && w_bf16->is_contiguous() &&
-                    (reinterpret_cast<uintptr_t>(w_bf16->data_ptr()) & 15) == 0,
-                "w_bf16 must be a 16-byte aligned contiguous bf16 arena of w's size");
-    a.w_bf16 = reinterpret_cast<uint16_t*>(w_bf16->data_ptr());
-  }
-  if (lr_mult.has_value() && lr_mult->defined()) {
-    check_f32(*lr_mult, "lr_mult");
-    a.lr_mult = lr_mult->data_ptr<float>();
-  }
+  set_chunks(a, chunks);
+  set_optional(a, w, grad_scale, w_bf16, lr_mult);
   c10::DeviceGuard guard(w.device());
   gk::fused_sgd(a, cur_stream(w));
 }
 
-void fused_adam(at::Tensor w, at::Tensor m, at::Tensor v, at::Tensor g, at::Tensor chunks, at::Tensor step,
-                std::vector<double> lr, std::vector<double> beta1, std::vector<double> beta2,
-                std::vector<double> eps, std::vector<double> weight_decay, std::vector<int64_t> decoupled,
-                bool zero_grad, c10::optional<at::Tensor> grad_scale, c10::optional<at::Tensor> w_bf16,
-                c10::optional<at::Tensor> lr_mult) {
-  check_f32(w, "w");
-  check_f32(m, "m");
-  check_f32(v, "v");
-  check_f32(g, "g");
+// What Adam and LAMB marshal alike: the four arenas, the step count, the chunk table, the optional tensors.
+void set_moment_args(gk::MomentArgs& a, const at::Tensor& w, const at::Tensor& m, const at::Tensor& v,
+                     const at::Tensor& g, const at::Tensor& chunks, const at::Tensor& step, size_t ng, bool zero_grad,
+                     const OptTensor& grad_scale, const OptTensor& w_bf16, const OptTensor& lr_mult) {
+  check_arenas({{"w", w}, {"m", m}, {"v", v}, {"g", g}}, "w/m/v/g size mismatch");
   check_f32(step, "step");
-  check_chunks(chunks);
-  const size_t ng = lr.size();
-  TORCH_CHECK(ng >= 1 && ng <= (size_t)gk::kMaxGroups, "1..8 param groups supported");
-  TORCH_CHECK(beta1.size() == ng && beta2.size() == ng && eps.size() == ng && weight_decay.size() == ng &&
-                  decoupled.size() == ng,
-              "hyper-parameter lists must have one entry per group");
-  TORCH_CHECK(w.numel() == g.numel() && m.numel() == w.numel() && v.numel() == w.numel(),
-              "w/m/v/g size mismatch");
   TORCH_CHECK(step.numel() == 1, "step must be one fp32 device scalar");
-  TORCH_CHECK(((reinterpret_cast<uintptr_t>(w.data_ptr()) | reinterpret_cast<uintptr_t>(g.data_ptr()) |
-                reinterpret_cast<uintptr_t>(m.data_ptr()) | reinterpret_cast<uintptr_t>(v.data_ptr())) & 15) == 0,
-              "arenas must be 16-byte aligned");
-  gk::AdamArgs a;
   a.w = w.data_ptr<float>();
   a.m = m.data_ptr<float>();
   a.v = v.data_ptr<float>();
   a.g = g.data_ptr<float>();
   a.step = step.data_ptr<float>();
-  for (size_t i = 0; i < ng; ++i) {
-    a.groups[i].lr = lr[i];
-    a.groups[i].beta1 = beta1[i];
-    a.groups[i].beta2 = beta2[i];
-    TORCH_CHECK(eps[i] > 0.0, "eps must be positive (eps = 0 turns the zero padding slots into 0 / 0)");
-    a.groups[i].eps = eps[i];
-    a.groups[i].weight_decay = weight_decay[i];
-    a.groups[i].decoupled = (int)decoupled[i];
-    a.groups[i].pad0 = 0;
-  }
-  for (size_t i = ng; i < (size_t)gk::kMaxGroups; ++i) a.groups[i] = gk::AdamGroup{0, 0, 0, 0, 0, 0, 0};
   a.ngroups = (int)ng;
-  a.chunks = reinterpret_cast<const gk::Chunk*>(chunks.data_ptr<int64_t>());
-  a.nchunks = (int)(chunks.numel() / 2);
   a.zero_grad = zero_grad ? 1 : 0;
-  if (grad_scale.has_value() && grad_scale->defined()) {
-    check_f32(*grad_scale, "grad_scale");
-    a.grad_scale = grad_scale->data_ptr<float>();
-  }
-  if (w_bf16.has_value() && w_bf16->defined()) {
-    TORCH_CHECK(w_bf16->scalar_type() == at::kBFloat16 && w_bf16->numel() == w.numel() && w_bf16->is_contiguous() &&
-                    (reinterpret_cast<uintptr_t>(w_bf16->data_ptr()) & 15) == 0,
-                "w_bf16 must be a 16-byte aligned contiguous bf16 arena of w's size");
-    a.w_bf16 = reinterpret_cast<uint16_t*>(w_bf16->data_ptr());
-  }
-  if (lr_mult.has_value() && lr_mult->defined()) {
-    check_f32(*lr_mult, "lr_mult");
-    a.lr_mult = lr_mult->data_ptr<float>();
-  }
+  set_chunks(a, chunks);
+  set_optional(a, w, grad_scale, w_bf16, lr_mult);
+}
+
+gk::AdamHyper adam_hyper(double lr, double beta1, double beta2, double eps, double weight_decay) {
+  TORCH_CHECK(eps > 0.0, "eps must be positive (eps = 0 turns the zero padding slots into 0 / 0)");
+  return {lr, beta1, beta2, eps, weight_decay};
+}
+
+void fused_adam(at::Tensor w, at::Tensor m, at::Tensor v, at::Tensor g, at::Tensor chunks, at::Tensor step,
+                std::vector<double> lr, std::vector<double> beta1, std::vector<double> beta2,
+                std::vector<double> eps, std::vector<double> weight_decay, std::vector<int64_t> decoupled,
+                bool zero_grad, OptTensor grad_scale, OptTensor w_bf16, OptTensor lr_mult) {
+  const size_t ng = lr.size();
+  check_groups(ng, {beta1.size(), beta2.size(), eps.size(), weight_decay.size(), decoupled.size()});
+  gk::AdamArgs a;
+  set_moment_args(a, w, m, v, g, chunks, step, ng, zero_grad, grad_scale, w_bf16, lr_mult);
+  for (size_t i = 0; i < ng; ++i)
+    a.groups[i] = {adam_hyper(lr[i], beta1[i], beta2[i], eps[i], weight_decay[i]), (int)decoupled[i], 0};
   c10::DeviceGuard guard(w.device());
   gk::fused_adam(a, cur_stream(w));
 }
@@ -362,83 +371,32 @@ void fused_lamb(at::Tensor w, at::Tensor m, at::Tensor v, at::Tensor g, at::Tens
                 at::Tensor seg_range, at::Tensor part, at::Tensor trust, std::vector<double> lr,
                 std::vector<double> beta1, std::vector<double> beta2, std::vector<double> eps,
                 std::vector<double> weight_decay, std::vector<int64_t> adapt, std::vector<double> trust_clip,
-                bool zero_grad, c10::optional<at::Tensor> grad_scale, c10::optional<at::Tensor> w_bf16,
-                c10::optional<at::Tensor> lr_mult, int64_t passes) {
-  check_f32(w, "w");
-  check_f32(m, "m");
-  check_f32(v, "v");
-  check_f32(g, "g");
-  check_f32(step, "step");
+                bool zero_grad, OptTensor grad_scale, OptTensor w_bf16, OptTensor lr_mult, int64_t passes) {
+  const size_t ng = lr.size();
+  check_groups(ng, {beta1.size(), beta2.size(), eps.size(), weight_decay.size(), adapt.size(), trust_clip.size()});
+  gk::LambArgs a;
+  set_moment_args(a, w, m, v, g, chunks, step, ng, zero_grad, grad_scale, w_bf16, lr_mult);
   check_f32(trust, "trust");
-  check_chunks(chunks);
   check_dev(seg_range, "seg_range");
   check_dev(part, "part");
-  const size_t ng = lr.size();
-  TORCH_CHECK(ng >= 1 && ng <= (size_t)gk::kMaxGroups, "1..8 param groups supported");
-  TORCH_CHECK(beta1.size() == ng && beta2.size() == ng && eps.size() == ng && weight_decay.size() == ng &&
-                  adapt.size() == ng && trust_clip.size() == ng,
-              "hyper-parameter lists must have one entry per group");
-  TORCH_CHECK(w.numel() == g.numel() && m.numel() == w.numel() && v.numel() == w.numel(),
-              "w/m/v/g size mismatch");
-  TORCH_CHECK(step.numel() == 1, "step must be one fp32 device scalar");
-  TORCH_CHECK(((reinterpret_cast<uintptr_t>(w.data_ptr()) | reinterpret_cast<uintptr_t>(g.data_ptr()) |
-                reinterpret_cast<uintptr_t>(m.data_ptr()) | reinterpret_cast<uintptr_t>(v.data_ptr())) & 15) == 0,
-              "arenas must be 16-byte aligned");
-  const int64_t nchunks = chunks.numel() / 2;
   const int64_t nseg = trust.numel();
-  TORCH_CHECK(seg_range.scalar_type() == at::kInt && seg_range.is_contiguous() && seg_range.numel() == 2 * nseg,
+  TORCH_CHECK(seg_range.scalar_type() == at::kInt && seg_range.numel() == 2 * nseg,
               "seg_range must be int32[2 * nseg]");
-  TORCH_CHECK(part.scalar_type() == at::kDouble && part.is_contiguous() && part.numel() >= 2 * nchunks,
+  TORCH_CHECK(part.scalar_type() == at::kDouble && part.numel() >= 2 * (int64_t)a.nchunks,
               "part must be float64[2 * nchunks]: the workspace belongs to another chunk table");
-  TORCH_CHECK(trust.is_contiguous(), "trust must be contiguous");
-  gk::LambArgs a;
-  a.w = w.data_ptr<float>();
-  a.m = m.data_ptr<float>();
-  a.v = v.data_ptr<float>();
-  a.g = g.data_ptr<float>();
-  a.step = step.data_ptr<float>();
-  for (size_t i = 0; i < ng; ++i) {
-    a.groups[i].lr = lr[i];
-    a.groups[i].beta1 = beta1[i];
-    a.groups[i].beta2 = beta2[i];
-    TORCH_CHECK(eps[i] > 0.0, "eps must be positive (eps = 0 turns the zero padding slots into 0 / 0)");
-    a.groups[i].eps = eps[i];
-    a.groups[i].weight_decay = weight_decay[i];
-    a.groups[i].trust_clip = trust_clip[i];
-    a.groups[i].adapt = (int)adapt[i];
-    a.groups[i].pad0 = 0;
-  }
-  for (size_t i = ng; i < (size_t)gk::kMaxGroups; ++i) a.groups[i] = gk::LambGroup{0, 0, 0, 0, 0, 0, 0, 0};
-  a.ngroups = (int)ng;
-  a.chunks = reinterpret_cast<const gk::Chunk*>(chunks.data_ptr<int64_t>());
-  a.nchunks = (int)nchunks;
-  a.zero_grad = zero_grad ? 1 : 0;
+  for (size_t i = 0; i < ng; ++i)
+    a.groups[i] = {adam_hyper(lr[i], beta1[i], beta2[i], eps[i], weight_decay[i]), trust_clip[i], (int)adapt[i], 0};
   a.seg_range = seg_range.data_ptr<int32_t>();
   a.nseg = (int)nseg;
   a.part = part.data_ptr<double>();
   a.trust = trust.data_ptr<float>();
   a.passes = (int)passes;
-  if (grad_scale.has_value() && grad_scale->defined()) {
-    check_f32(*grad_scale, "grad_scale");
-    a.grad_scale = grad_scale->data_ptr<float>();
-  }
-  if (w_bf16.has_value() && w_bf16->defined()) {
-    TORCH_CHECK(w_bf16->scalar_type() == at::kBFloat16 && w_bf16->numel() == w.numel() && w_bf16->is_contiguous() &&
-                    (reinterpret_cast<uintptr_t>(w_bf16->data_ptr()) & 15) == 0,
-                "w_bf16 must be a 16-byte aligned contiguous bf16 arena of w's size");
-    a.w_bf16 = reinterpret_cast<uint16_t*>(w_bf16->data_ptr());
-  }
-  if (lr_mult.has_value() && lr_mult->defined()) {
-    check_f32(*lr_mult, "lr_mult");
-    a.lr_mult = lr_mult->data_ptr<float>();
-  }
   c10::DeviceGuard guard(w.device());
   gk::fused_lamb(a, cur_stream(w));
 }
 
 void segmented_sumsq(at::Tensor w, at::Tensor g, at::Tensor chunks, at::Tensor out) {
-  check_f32(w, "w");
-  check_f32(g, "g");
+  check_arenas({{"w", w}, {"g", g}}, "w/g size mismatch");
   check_chunks(chunks);
   check_dev(out, "out");
   TORCH_CHECK(out.scalar_type() == at::kDouble, "out must be float64[2*nseg]");
@@ -451,19 +409,15 @@ void segmented_sumsq(at::Tensor w, at::Tensor g, at::Tensor chunks, at::Tensor o
 void fused_lars(at::Tensor w, at::Tensor m, at::Tensor g, at::Tensor chunks, at::Tensor seg_sumsq,
                 std::vector<double> lr, std::vector<double> momentum, std::vector<double> weight_decay,
                 std::vector<double> eeta, std::vector<double> epsilon) {
-  check_f32(w, "w");
-  check_f32(m, "m");
-  check_f32(g, "g");
-  check_chunks(chunks);
-  check_dev(seg_sumsq, "seg_sumsq");
   const size_t ng = lr.size();
-  TORCH_CHECK(ng >= 1 && ng <= (size_t)gk::kMaxGroups, "1..8 param groups supported");
+  check_groups(ng, {momentum.size(), weight_decay.size(), eeta.size(), epsilon.size()});
+  check_arenas({{"w", w}, {"m", m}, {"g", g}}, "w/m/g size mismatch");
+  check_dev(seg_sumsq, "seg_sumsq");
   gk::LarsArgs a;
   a.w = w.data_ptr<float>();
   a.m = m.data_ptr<float>();
   a.g = g.data_ptr<float>();
-  a.chunks = reinterpret_cast<const gk::Chunk*>(chunks.data_ptr<int64_t>());
-  a.nchunks = (int)(chunks.numel() / 2);
+  set_chunks(a, chunks);
   a.seg_sumsq = seg_sumsq.data_ptr<double>();
   for (size_t i = 0; i < ng; ++i) {
     a.lr[i] = (float)lr[i];
@@ -912,22 +866,14 @@ void bn_relu_pool_backward(at::Tensor dy, at::Tensor amax, at::Tensor x, at::Ten
 // ---------------------------------------------------------------------------
 void momentum_correct(at::Tensor u, at::Tensor g, at::Tensor w, at::Tensor chunks, int64_t begin, int64_t count,
                       std::vector<double> momentum, std::vector<double> weight_decay) {
-  check_f32(u, "u");
-  check_f32(g, "g");
-  check_f32(w, "w");
-  check_chunks(chunks);
-  TORCH_CHECK(u.numel() == g.numel() && w.numel() == g.numel(), "arena size mismatch");
-  for (const at::Tensor* t : {&u, &g, &w})
-    TORCH_CHECK((reinterpret_cast<uintptr_t>(t->data_ptr()) & 15) == 0, "arenas must be 16-byte aligned");
-  TORCH_CHECK(begin >= 0 && count >= 0 && (begin + count) * 2 <= chunks.numel(), "chunk range out of bounds");
   const size_t ng = momentum.size();
-  TORCH_CHECK(ng >= 1 && ng <= (size_t)gk::kMaxGroups && weight_decay.size() == ng, "1..8 param groups");
+  check_groups(ng, {weight_decay.size()}, "1..8 param groups");
+  check_arenas({{"u", u}, {"g", g}, {"w", w}}, "arena size mismatch");
   gk::McArgs a;
   a.u = u.data_ptr<float>();
   a.g = g.data_ptr<float>();
   a.w = w.data_ptr<float>();
-  a.chunks = reinterpret_cast<const gk::Chunk*>(chunks.data_ptr<int64_t>()) + begin;
-  a.nchunks = (int)count;
+  set_chunks(a, chunks, begin, count);
   for (size_t i = 0; i < ng; ++i) {
     a.momentum[i] = (float)momentum[i];
     a.weight_decay[i] = (float)weight_decay[i];

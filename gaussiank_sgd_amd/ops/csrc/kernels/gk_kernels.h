@@ -186,49 +186,48 @@ struct Chunk {
 constexpr int kChunkElems = 16384;
 constexpr int kMaxGroups = 8;
 
+// What fused SGD, Adam and LAMB take alike: the arenas, the chunk table and the optional device tensors.
+struct ArenaArgs {
+  float* w = nullptr;
+  float* m = nullptr;        // SGD: momentum buffer, may be null when no group uses momentum; Adam, LAMB: exp_avg
+  float* g = nullptr;
+  const Chunk* chunks = nullptr;
+  int nchunks = 0;
+  int ngroups = 0;
+  int zero_grad = 1;
+  const float* grad_scale = nullptr;  // optional device scalar (clip coefficient)
+  uint16_t* w_bf16 = nullptr;         // optional bf16 shadow of w written in the same pass
+  const float* lr_mult = nullptr;     // optional device scalar multiplying every group's lr (graph replay)
+};
+
 struct SgdGroup {
   float lr, momentum, dampening, weight_decay;
   int nesterov;
   int first_step;     // momentum buffer not yet initialised -> buf = d
   float pad0, pad1;
 };
-struct SgdArgs {
-  float* w = nullptr;
-  float* m = nullptr;        // may be null when no group uses momentum
-  float* g = nullptr;
-  const Chunk* chunks = nullptr;
-  int nchunks = 0;
-  SgdGroup groups[kMaxGroups];
-  int ngroups = 0;
-  int zero_grad = 1;
-  const float* grad_scale = nullptr;  // optional device scalar (clip coefficient)
-  uint16_t* w_bf16 = nullptr;         // optional bf16 shadow of w written in the same pass
-  const float* lr_mult = nullptr;     // optional device scalar multiplying every group's lr (graph replay)
+struct SgdArgs : ArenaArgs {
+  SgdGroup groups[kMaxGroups] = {};
 };
 void fused_sgd(const SgdArgs& a, hipStream_t stream);
 
 // torch.optim.Adam / AdamW (single-tensor, no amsgrad / maximize) over the
 // same chunk table.  The hyper-parameters stay double: torch derives the bias
 // corrections, lr / bc1 and 1 - lr * wd from Python floats before it rounds.
-struct AdamGroup {
+struct AdamHyper {
   double lr, beta1, beta2, eps, weight_decay;
+};
+struct AdamGroup : AdamHyper {
   int decoupled;      // AdamW: w *= 1 - lr * wd; otherwise g += wd * w
   int pad0;
 };
-struct AdamArgs {
-  float* w = nullptr;
-  float* m = nullptr;        // exp_avg
+// Adam's and LAMB's state beside ArenaArgs
+struct MomentArgs : ArenaArgs {
   float* v = nullptr;        // exp_avg_sq
-  float* g = nullptr;
-  const Chunk* chunks = nullptr;
-  int nchunks = 0;
-  AdamGroup groups[kMaxGroups];
-  int ngroups = 0;
-  int zero_grad = 1;
-  float* step = nullptr;              // device step count (fp32 scalar, torch's capturable convention)
-  const float* grad_scale = nullptr;  // optional device scalar (clip coefficient)
-  uint16_t* w_bf16 = nullptr;         // optional bf16 shadow of w written in the same pass
-  const float* lr_mult = nullptr;     // optional device scalar multiplying every group's lr (graph replay)
+  float* step = nullptr;     // device step count (fp32 scalar, torch's capturable convention)
+};
+struct AdamArgs : MomentArgs {
+  AdamGroup groups[kMaxGroups] = {};
 };
 // Two launches on `stream`: *step += 1 (one thread), then the update, whose
 // workgroups read the new count for the bias corrections.  No host read.
@@ -236,26 +235,13 @@ void fused_adam(const AdamArgs& a, hipStream_t stream);
 
 // LAMB: Adam's moments, u = mhat / (sqrt(vhat) + eps) + wd * w, and per tensor
 // (segment of the chunk table) trust = ||w|| / ||u||; w -= lr * trust * u.
-struct LambGroup {
-  double lr, beta1, beta2, eps, weight_decay;
+struct LambGroup : AdamHyper {
   double trust_clip;  // upper bound of the trust ratio; 0: none
   int adapt;          // 0: trust = 1 (AdamW with decoupled decay)
   int pad0;
 };
-struct LambArgs {
-  float* w = nullptr;
-  float* m = nullptr;        // exp_avg
-  float* v = nullptr;        // exp_avg_sq
-  float* g = nullptr;
-  const Chunk* chunks = nullptr;
-  int nchunks = 0;
-  LambGroup groups[kMaxGroups];
-  int ngroups = 0;
-  int zero_grad = 1;
-  float* step = nullptr;              // device step count, as AdamArgs::step
-  const float* grad_scale = nullptr;
-  uint16_t* w_bf16 = nullptr;
-  const float* lr_mult = nullptr;
+struct LambArgs : MomentArgs {
+  LambGroup groups[kMaxGroups] = {};
   const int32_t* seg_range = nullptr; // [2 * nseg]: first chunk, number of chunks of every tensor
   int nseg = 0;
   double* part = nullptr;             // [2 * nchunks] workspace: per-chunk sum of w^2, of u^2

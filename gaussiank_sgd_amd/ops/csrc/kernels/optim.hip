@@ -25,7 +25,10 @@
 //
 // The arenas are float4-aligned per tensor (the Python arena pads every tensor
 // to 64 elements), so each workgroup streams one <=16K-element chunk with
-// 16-byte loads.
+// 16-byte loads.  for_chunk() is that loop: every chunk kernel states its
+// per-element arithmetic once, as a body over Vec<N>, and for_chunk runs it
+// with N = 4 over the chunk's float4s and with N = 1 over the up to 3 elements
+// left (a length the arena's padding never produces, but the ops accept it).
 #include "common.h"
 #include "gk_kernels.h"
 
@@ -37,6 +40,64 @@ __device__ __forceinline__ uint16_t f2bf(float f) {  // round-to-nearest-even, N
   if ((u & 0x7f800000u) == 0x7f800000u && (u & 0x7fffffu)) return (uint16_t)((u >> 16) | 0x40);
   u += 0x7fffu + ((u >> 16) & 1u);
   return (uint16_t)(u >> 16);
+}
+
+// ---- streaming one chunk --------------------------------------------------------
+// N consecutive floats in registers, moved by load / store as ONE access: 16 bytes for N = 4, a float for N = 1.
+template <int N>
+struct Vec {
+  float e[N];
+  __device__ __forceinline__ float& operator[](int j) { return e[j]; }
+  __device__ __forceinline__ float operator[](int j) const { return e[j]; }
+};
+template <int N>
+struct Width { static constexpr int value = N; };
+
+template <int N>
+using Packed = float __attribute__((ext_vector_type(N)));   // the access: global_load / global_store_dwordx4 for N = 4
+template <int N>
+__device__ __forceinline__ Vec<N> load(const float* p, int i) {
+  const Packed<N> t = reinterpret_cast<const Packed<N>*>(p)[i];
+  Vec<N> v;
+#pragma unroll
+  for (int j = 0; j < N; ++j) v[j] = t[j];
+  return v;
+}
+template <int N>
+__device__ __forceinline__ void store(float* p, int i, const Vec<N>& v) {
+  Packed<N> t;
+#pragma unroll
+  for (int j = 0; j < N; ++j) t[j] = v[j];
+  reinterpret_cast<Packed<N>*>(p)[i] = t;
+}
+
+// bf16 shadow of N new weights: one 8-byte store for N = 4
+template <int N>
+__device__ __forceinline__ void store_shadow(uint16_t* s, int i, const Vec<N>& w) {
+  if constexpr (N == 4) {
+    const uint32_t lo = (uint32_t)f2bf(w[0]) | ((uint32_t)f2bf(w[1]) << 16);
+    const uint32_t hi = (uint32_t)f2bf(w[2]) | ((uint32_t)f2bf(w[3]) << 16);
+    reinterpret_cast<uint2*>(s)[i] = make_uint2(lo, hi);
+  } else {
+    s[i] = f2bf(w[0]);
+  }
+}
+
+// The sum of squares as the norms (LAMB, LARS) define it: (x^2 + y^2) + (z^2 + w^2) for a float4, one square at a
+// time in the tail.  The trust ratios are bit-identical across replicas only while this association holds.
+template <int N>
+__device__ __forceinline__ float sumsq(const Vec<N>& a) {
+  if constexpr (N == 4) return (a[0] * a[0] + a[1] * a[1]) + (a[2] * a[2] + a[3] * a[3]);
+  else return a[0] * a[0];
+}
+
+// body(Width<4>(), i) for every float4 i of a chunk of `len` elements, then body(Width<1>(), i) for the elements
+// behind the last whole float4; i indexes units of N floats from the chunk's start, as load / store take it.
+template <class Body>
+__device__ __forceinline__ void for_chunk(int len, Body body) {
+  const int n4 = len >> 2;
+  for (int i = threadIdx.x; i < n4; i += kBlock) body(Width<4>(), i);
+  for (int i = (n4 << 2) + threadIdx.x; i < len; i += kBlock) body(Width<1>(), i);
 }
 
 __device__ __forceinline__ float sgd_elem(float w, float& m, float g, const SgdGroup& p, float gs) {
@@ -58,87 +119,88 @@ __global__ __launch_bounds__(kBlock) void fused_sgd_kernel(SgdArgs a) {
   float* w = a.w + c.start;
   float* m = a.m ? a.m + c.start : nullptr;
   float* g = a.g + c.start;
+  uint16_t* shadow = a.w_bf16 ? a.w_bf16 + c.start : nullptr;
   const bool use_m = p.momentum != 0.f;
-  const int n4 = c.len >> 2;
-  float4* w4 = reinterpret_cast<float4*>(w);
-  float4* g4 = reinterpret_cast<float4*>(g);
-  float4* m4 = reinterpret_cast<float4*>(m);
-  for (int i = threadIdx.x; i < n4; i += kBlock) {
-    float4 wv = w4[i];
-    const float4 gv = g4[i];
-    float4 mv = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (use_m && !p.first_step) mv = m4[i];
-    wv.x = sgd_elem(wv.x, mv.x, gv.x, p, gs);
-    wv.y = sgd_elem(wv.y, mv.y, gv.y, p, gs);
-    wv.z = sgd_elem(wv.z, mv.z, gv.z, p, gs);
-    wv.w = sgd_elem(wv.w, mv.w, gv.w, p, gs);
-    w4[i] = wv;
-    if (use_m) m4[i] = mv;
-    if (a.zero_grad) g4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (a.w_bf16) {
-      const uint32_t lo = (uint32_t)f2bf(wv.x) | ((uint32_t)f2bf(wv.y) << 16);
-      const uint32_t hi = (uint32_t)f2bf(wv.z) | ((uint32_t)f2bf(wv.w) << 16);
-      reinterpret_cast<uint2*>(a.w_bf16 + c.start)[i] = make_uint2(lo, hi);
-    }
-  }
-  for (int i = (n4 << 2) + threadIdx.x; i < c.len; i += kBlock) {
-    float mv = (use_m && !p.first_step) ? m[i] : 0.f;
-    w[i] = sgd_elem(w[i], mv, g[i], p, gs);
-    if (use_m) m[i] = mv;
-    if (a.zero_grad) g[i] = 0.f;
-    if (a.w_bf16) a.w_bf16[c.start + i] = f2bf(w[i]);
-  }
+  for_chunk(c.len, [&](auto width, int i) {
+    constexpr int N = decltype(width)::value;
+    Vec<N> wv = load<N>(w, i);
+    const Vec<N> gv = load<N>(g, i);
+    Vec<N> mv = {};
+    if (use_m && !p.first_step) mv = load<N>(m, i);
+#pragma unroll
+    for (int j = 0; j < N; ++j) wv[j] = sgd_elem(wv[j], mv[j], gv[j], p, gs);
+    store<N>(w, i, wv);
+    if (use_m) store<N>(m, i, mv);
+    if (a.zero_grad) store<N>(g, i, Vec<N>{});
+    if (shadow) store_shadow<N>(shadow, i, wv);
+  });
 }
 
-// ---- Adam / AdamW -------------------------------------------------------------
+// ---- Adam / AdamW and LAMB: one core --------------------------------------------
 // Per-workgroup constants of one chunk's param group at the current step.
 struct AdamCoef {
   float omb1, beta2, omb2;   // 1 - beta1, beta2, 1 - beta2
-  float decay;               // AdamW: 1 - lr * wd (1 when coupled)
-  float wd;                  // Adam: wd added to the gradient (0 when decoupled)
-  float step_size;           // lr / (1 - beta1^t)
+  float bc1;                 // 1 - beta1^t
   float bc2_sqrt;            // sqrt(1 - beta2^t)
   float eps;
-};
+  float wd;                  // weight decay added as wd * w: to the gradient (Adam, 0 when decoupled), to u (LAMB)
+  float decay;               // AdamW: 1 - lr * wd (1 when coupled)
+  float step_size;           // lr / (1 - beta1^t)
+  double lr;                 // lr * lr_mult; read by lamb_apply_kernel alone, which scales it by the trust ratio
+};                           // (a kernel's unused fields cost nothing: the compiler drops them from its LDS copy)
+
+// Thread 0 of a workgroup: the bias corrections from the device step count, in double (torch derives them, lr / bc1
+// and 1 - lr * wd from Python floats before it rounds); once per workgroup, then through LDS -- a per-element pow
+// would make the streaming passes compute-bound.
+__device__ __forceinline__ AdamCoef adam_coef(const AdamHyper& p, bool decoupled, const float* step,
+                                              const float* lr_mult) {
+  const double t = (double)*step;
+  AdamCoef k;
+  k.lr = p.lr;
+  if (lr_mult) k.lr *= (double)*lr_mult;   // lr schedule of a captured graph; scales the decoupled decay too
+  const double bc1 = 1.0 - pow(p.beta1, t);
+  const double bc2 = 1.0 - pow(p.beta2, t);
+  k.omb1 = (float)(1.0 - p.beta1);
+  k.beta2 = (float)p.beta2;
+  k.omb2 = (float)(1.0 - p.beta2);
+  k.bc1 = (float)bc1;
+  k.bc2_sqrt = (float)sqrt(bc2);
+  k.eps = (float)p.eps;
+  k.wd = decoupled ? 0.f : (float)p.weight_decay;
+  k.decay = decoupled ? (float)(1.0 - k.lr * p.weight_decay) : 1.f;
+  k.step_size = (float)(k.lr / bc1);
+  return k;
+}
 
 __global__ void adam_tick_kernel(float* __restrict__ step) { *step += 1.f; }
 
-// torch's single-tensor order of operations; sqrtf and '/' are the correctly
-// rounded ones (with eps = 1e-8 and the tiny v of a sparsified gradient the
-// approximate rcp / rsq are visible).  A slot with w = g = m = v = 0 (padding)
-// stays exactly 0 because eps > 0 (checked by the binding): 0 / (0 + eps).
+// The moments from the scaled gradient d, in torch's forms (lerp; mul, addcmul).  Adam and LAMB share state that a
+// wrapped optimizer hands from one to the other, and LAMB without adaptation is bit-for-bit AdamW: one copy.
+__device__ __forceinline__ void adam_moments(float& m, float& v, float d, const AdamCoef& k) {
+  m = fmaf(k.omb1, d - m, m);
+  v = fmaf(k.omb2 * d, d, k.beta2 * v);
+}
+
+// sqrt(vhat) + eps.  sqrtf and '/' are the correctly rounded ones (with eps = 1e-8 and the tiny v of a sparsified
+// gradient the approximate rcp / rsq are visible).
+__device__ __forceinline__ float adam_denom(float v, const AdamCoef& k) { return sqrtf(v) / k.bc2_sqrt + k.eps; }
+
+// torch's single-tensor order of operations.  A slot with w = g = m = v = 0 (padding) stays exactly 0 because
+// eps > 0 (checked by the binding): 0 / (0 + eps).
 __device__ __forceinline__ float adam_elem(float w, float& m, float& v, float g, const AdamCoef& k, float gs) {
   float d = g * gs;
   if (k.wd != 0.f) d = fmaf(k.wd, w, d);
   w *= k.decay;
-  m = fmaf(k.omb1, d - m, m);
-  v = fmaf(k.omb2 * d, d, k.beta2 * v);
-  const float denom = sqrtf(v) / k.bc2_sqrt + k.eps;
-  return fmaf(-k.step_size, m / denom, w);
+  adam_moments(m, v, d, k);
+  return fmaf(-k.step_size, m / adam_denom(v, k), w);
 }
 
 __global__ __launch_bounds__(kBlock) void fused_adam_kernel(AdamArgs a) {
   const Chunk c = a.chunks[blockIdx.x];
-  // bias corrections from the device step count, in double, once per workgroup
-  // (a per-element pow would make this streaming pass compute-bound)
   __shared__ AdamCoef sk;
   if (threadIdx.x == 0) {
     const AdamGroup p = a.groups[c.group];
-    const double t = (double)*a.step;
-    double lr = p.lr;
-    if (a.lr_mult) lr *= (double)*a.lr_mult;   // lr schedule of a captured graph; scales the decoupled decay too
-    const double bc1 = 1.0 - pow(p.beta1, t);
-    const double bc2 = 1.0 - pow(p.beta2, t);
-    AdamCoef k;
-    k.omb1 = (float)(1.0 - p.beta1);
-    k.beta2 = (float)p.beta2;
-    k.omb2 = (float)(1.0 - p.beta2);
-    k.decay = p.decoupled ? (float)(1.0 - lr * p.weight_decay) : 1.f;
-    k.wd = p.decoupled ? 0.f : (float)p.weight_decay;
-    k.step_size = (float)(lr / bc1);
-    k.bc2_sqrt = (float)sqrt(bc2);
-    k.eps = (float)p.eps;
-    sk = k;
+    sk = adam_coef(p, p.decoupled != 0, a.step, a.lr_mult);
   }
   __syncthreads();
   const AdamCoef k = sk;
@@ -147,126 +209,62 @@ __global__ __launch_bounds__(kBlock) void fused_adam_kernel(AdamArgs a) {
   float* m = a.m + c.start;
   float* v = a.v + c.start;
   float* g = a.g + c.start;
-  const int n4 = c.len >> 2;
-  float4* w4 = reinterpret_cast<float4*>(w);
-  float4* m4 = reinterpret_cast<float4*>(m);
-  float4* v4 = reinterpret_cast<float4*>(v);
-  float4* g4 = reinterpret_cast<float4*>(g);
-  for (int i = threadIdx.x; i < n4; i += kBlock) {
-    float4 wv = w4[i];
-    float4 mv = m4[i];
-    float4 vv = v4[i];
-    const float4 gv = g4[i];
-    wv.x = adam_elem(wv.x, mv.x, vv.x, gv.x, k, gs);
-    wv.y = adam_elem(wv.y, mv.y, vv.y, gv.y, k, gs);
-    wv.z = adam_elem(wv.z, mv.z, vv.z, gv.z, k, gs);
-    wv.w = adam_elem(wv.w, mv.w, vv.w, gv.w, k, gs);
-    w4[i] = wv;
-    m4[i] = mv;
-    v4[i] = vv;
-    if (a.zero_grad) g4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (a.w_bf16) {
-      const uint32_t lo = (uint32_t)f2bf(wv.x) | ((uint32_t)f2bf(wv.y) << 16);
-      const uint32_t hi = (uint32_t)f2bf(wv.z) | ((uint32_t)f2bf(wv.w) << 16);
-      reinterpret_cast<uint2*>(a.w_bf16 + c.start)[i] = make_uint2(lo, hi);
-    }
-  }
-  for (int i = (n4 << 2) + threadIdx.x; i < c.len; i += kBlock) {
-    float mv = m[i], vv = v[i];
-    const float wn = adam_elem(w[i], mv, vv, g[i], k, gs);
-    w[i] = wn;
-    m[i] = mv;
-    v[i] = vv;
-    if (a.zero_grad) g[i] = 0.f;
-    if (a.w_bf16) a.w_bf16[c.start + i] = f2bf(wn);
-  }
+  uint16_t* shadow = a.w_bf16 ? a.w_bf16 + c.start : nullptr;
+  for_chunk(c.len, [&](auto width, int i) {
+    constexpr int N = decltype(width)::value;
+    Vec<N> wv = load<N>(w, i), mv = load<N>(m, i), vv = load<N>(v, i);
+    const Vec<N> gv = load<N>(g, i);
+#pragma unroll
+    for (int j = 0; j < N; ++j) wv[j] = adam_elem(wv[j], mv[j], vv[j], gv[j], k, gs);
+    store<N>(w, i, wv);
+    store<N>(m, i, mv);
+    store<N>(v, i, vv);
+    if (a.zero_grad) store<N>(g, i, Vec<N>{});
+    if (shadow) store_shadow<N>(shadow, i, wv);
+  });
 }
 
 // ---- LAMB ---------------------------------------------------------------------
-// Per-workgroup constants of one chunk's param group at the current step.
-struct LambCoef {
-  float omb1, beta2, omb2;   // 1 - beta1, beta2, 1 - beta2
-  float bc1;                 // 1 - beta1^t
-  float bc2_sqrt;            // sqrt(1 - beta2^t)
-  float eps, wd;
-};
-
-// thread 0 of the workgroup; bias corrections in double from the device step count, as fused_adam_kernel
-__device__ __forceinline__ LambCoef lamb_coef(const LambGroup& p, const float* step) {
-  const double t = (double)*step;
-  LambCoef k;
-  k.omb1 = (float)(1.0 - p.beta1);
-  k.beta2 = (float)p.beta2;
-  k.omb2 = (float)(1.0 - p.beta2);
-  k.bc1 = (float)(1.0 - pow(p.beta1, t));
-  k.bc2_sqrt = (float)sqrt(1.0 - pow(p.beta2, t));
-  k.eps = (float)p.eps;
-  k.wd = (float)p.weight_decay;
-  return k;
-}
-
-// The moment update of adam_elem (same forms).
-__device__ __forceinline__ void lamb_moments(float& m, float& v, float g, const LambCoef& k, float gs) {
-  const float d = g * gs;
-  m = fmaf(k.omb1, d - m, m);
-  v = fmaf(k.omb2 * d, d, k.beta2 * v);
+// LAMB's coefficients: Adam's with the decay kept out of the gradient (k.wd goes into u).
+__device__ __forceinline__ AdamCoef lamb_coef(const LambArgs& a, const Chunk& c) {
+  return adam_coef(a.groups[c.group], false, a.step, a.lr_mult);
 }
 
 // The update direction from the UPDATED moments; both streaming passes call
-// this, so the u whose norm was taken is the u that is applied.  IEEE sqrt and
-// divisions for the reason given at adam_elem; a slot with w = m = v = 0
-// (padding) gives 0 / (0 + eps) + wd * 0 = 0 because eps > 0.
-__device__ __forceinline__ float lamb_u(float w, float m, float v, const LambCoef& k) {
-  const float denom = sqrtf(v) / k.bc2_sqrt + k.eps;
-  return fmaf(k.wd, w, (m / k.bc1) / denom);
+// this, so the u whose norm was taken is the u that is applied.  A slot with
+// w = m = v = 0 (padding) gives 0 / (0 + eps) + wd * 0 = 0 because eps > 0.
+__device__ __forceinline__ float lamb_u(float w, float m, float v, const AdamCoef& k) {
+  return fmaf(k.wd, w, (m / k.bc1) / adam_denom(v, k));
 }
 
 // Pass 1: m, v updated in place; the chunk's sum of w^2 and of u^2 to part[2 * chunk], part[2 * chunk + 1].
 // Each lane adds at most kChunkElems / kBlock = 64 squares in fp32; everything above that is double.
 __global__ __launch_bounds__(kBlock) void lamb_moments_kernel(LambArgs a) {
   const Chunk c = a.chunks[blockIdx.x];
-  __shared__ LambCoef sk;
+  __shared__ AdamCoef sk;
   __shared__ double sh[kWavesPerBlock];
-  if (threadIdx.x == 0) sk = lamb_coef(a.groups[c.group], a.step);
+  if (threadIdx.x == 0) sk = lamb_coef(a, c);
   __syncthreads();
-  const LambCoef k = sk;
+  const AdamCoef k = sk;
   const float gs = a.grad_scale ? *a.grad_scale : 1.f;
   const float* w = a.w + c.start;
   float* m = a.m + c.start;
   float* v = a.v + c.start;
   const float* g = a.g + c.start;
-  const int n4 = c.len >> 2;
-  const float4* w4 = reinterpret_cast<const float4*>(w);
-  float4* m4 = reinterpret_cast<float4*>(m);
-  float4* v4 = reinterpret_cast<float4*>(v);
-  const float4* g4 = reinterpret_cast<const float4*>(g);
   float sw = 0.f, su = 0.f;
-  for (int i = threadIdx.x; i < n4; i += kBlock) {
-    const float4 wv = w4[i];
-    float4 mv = m4[i];
-    float4 vv = v4[i];
-    const float4 gv = g4[i];
-    lamb_moments(mv.x, vv.x, gv.x, k, gs);
-    lamb_moments(mv.y, vv.y, gv.y, k, gs);
-    lamb_moments(mv.z, vv.z, gv.z, k, gs);
-    lamb_moments(mv.w, vv.w, gv.w, k, gs);
-    m4[i] = mv;
-    v4[i] = vv;
-    const float ux = lamb_u(wv.x, mv.x, vv.x, k), uy = lamb_u(wv.y, mv.y, vv.y, k);
-    const float uz = lamb_u(wv.z, mv.z, vv.z, k), uw = lamb_u(wv.w, mv.w, vv.w, k);
-    sw += (wv.x * wv.x + wv.y * wv.y) + (wv.z * wv.z + wv.w * wv.w);
-    su += (ux * ux + uy * uy) + (uz * uz + uw * uw);
-  }
-  for (int i = (n4 << 2) + threadIdx.x; i < c.len; i += kBlock) {
-    float mv = m[i], vv = v[i];
-    const float wv = w[i];
-    lamb_moments(mv, vv, g[i], k, gs);
-    m[i] = mv;
-    v[i] = vv;
-    const float u = lamb_u(wv, mv, vv, k);
-    sw += wv * wv;
-    su += u * u;
-  }
+  for_chunk(c.len, [&](auto width, int i) {
+    constexpr int N = decltype(width)::value;
+    const Vec<N> wv = load<N>(w, i), gv = load<N>(g, i);
+    Vec<N> mv = load<N>(m, i), vv = load<N>(v, i), u;
+#pragma unroll
+    for (int j = 0; j < N; ++j) adam_moments(mv[j], vv[j], gv[j] * gs, k);
+    store<N>(m, i, mv);
+    store<N>(v, i, vv);
+#pragma unroll
+    for (int j = 0; j < N; ++j) u[j] = lamb_u(wv[j], mv[j], vv[j], k);
+    sw += sumsq<N>(wv);
+    su += sumsq<N>(u);
+  });
   const double bw = block_sum((double)sw, sh);
   const double bu = block_sum((double)su, sh);
   if (threadIdx.x == 0) {
@@ -304,49 +302,32 @@ __global__ __launch_bounds__(kBlock) void lamb_trust_kernel(LambArgs a) {
 // Pass 3: w -= (lr * lr_mult * trust[seg]) * u, u recomputed from the updated moments.
 __global__ __launch_bounds__(kBlock) void lamb_apply_kernel(LambArgs a) {
   const Chunk c = a.chunks[blockIdx.x];
-  __shared__ LambCoef sk;
+  __shared__ AdamCoef sk;
   __shared__ float s_slr;
   if (threadIdx.x == 0) {
-    const LambGroup p = a.groups[c.group];
-    sk = lamb_coef(p, a.step);
-    double lr = p.lr;
-    if (a.lr_mult) lr *= (double)*a.lr_mult;   // lr schedule of a captured graph
+    const AdamCoef k = lamb_coef(a, c);
     const float trust = (c.seg >= 0 && c.seg < a.nseg) ? a.trust[c.seg] : 1.f;
-    s_slr = (float)(lr * (double)trust);
+    s_slr = (float)(k.lr * (double)trust);
+    sk = k;
   }
   __syncthreads();
-  const LambCoef k = sk;
+  const AdamCoef k = sk;
   const float nslr = -s_slr;
   float* w = a.w + c.start;
   const float* m = a.m + c.start;
   const float* v = a.v + c.start;
   float* g = a.g + c.start;
-  const int n4 = c.len >> 2;
-  float4* w4 = reinterpret_cast<float4*>(w);
-  const float4* m4 = reinterpret_cast<const float4*>(m);
-  const float4* v4 = reinterpret_cast<const float4*>(v);
-  for (int i = threadIdx.x; i < n4; i += kBlock) {
-    float4 wv = w4[i];
-    const float4 mv = m4[i];
-    const float4 vv = v4[i];
-    wv.x = fmaf(nslr, lamb_u(wv.x, mv.x, vv.x, k), wv.x);
-    wv.y = fmaf(nslr, lamb_u(wv.y, mv.y, vv.y, k), wv.y);
-    wv.z = fmaf(nslr, lamb_u(wv.z, mv.z, vv.z, k), wv.z);
-    wv.w = fmaf(nslr, lamb_u(wv.w, mv.w, vv.w, k), wv.w);
-    w4[i] = wv;
-    if (a.zero_grad) reinterpret_cast<float4*>(g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (a.w_bf16) {
-      const uint32_t lo = (uint32_t)f2bf(wv.x) | ((uint32_t)f2bf(wv.y) << 16);
-      const uint32_t hi = (uint32_t)f2bf(wv.z) | ((uint32_t)f2bf(wv.w) << 16);
-      reinterpret_cast<uint2*>(a.w_bf16 + c.start)[i] = make_uint2(lo, hi);
-    }
-  }
-  for (int i = (n4 << 2) + threadIdx.x; i < c.len; i += kBlock) {
-    const float wn = fmaf(nslr, lamb_u(w[i], m[i], v[i], k), w[i]);
-    w[i] = wn;
-    if (a.zero_grad) g[i] = 0.f;
-    if (a.w_bf16) a.w_bf16[c.start + i] = f2bf(wn);
-  }
+  uint16_t* shadow = a.w_bf16 ? a.w_bf16 + c.start : nullptr;
+  for_chunk(c.len, [&](auto width, int i) {
+    constexpr int N = decltype(width)::value;
+    Vec<N> wv = load<N>(w, i);
+    const Vec<N> mv = load<N>(m, i), vv = load<N>(v, i);
+#pragma unroll
+    for (int j = 0; j < N; ++j) wv[j] = fmaf(nslr, lamb_u(wv[j], mv[j], vv[j], k), wv[j]);
+    store<N>(w, i, wv);
+    if (a.zero_grad) store<N>(g, i, Vec<N>{});
+    if (shadow) store_shadow<N>(shadow, i, wv);
+  });
 }
 
 // DGC momentum correction: u = mu*u + (g + wd*w); g = u (the compressor then
@@ -358,23 +339,15 @@ __global__ __launch_bounds__(kBlock) void momentum_correct_kernel(McArgs a) {
   float* u = a.u + c.start;
   float* g = a.g + c.start;
   const float* w = a.w + c.start;
-  const int n4 = c.len >> 2;
-  for (int i = threadIdx.x; i < n4; i += kBlock) {
-    float4 uv = reinterpret_cast<float4*>(u)[i];
-    const float4 gv = reinterpret_cast<const float4*>(g)[i];
-    const float4 wv = reinterpret_cast<const float4*>(w)[i];
-    uv.x = fmaf(mu, uv.x, fmaf(wd, wv.x, gv.x));
-    uv.y = fmaf(mu, uv.y, fmaf(wd, wv.y, gv.y));
-    uv.z = fmaf(mu, uv.z, fmaf(wd, wv.z, gv.z));
-    uv.w = fmaf(mu, uv.w, fmaf(wd, wv.w, gv.w));
-    reinterpret_cast<float4*>(u)[i] = uv;
-    reinterpret_cast<float4*>(g)[i] = uv;
-  }
-  for (int i = (n4 << 2) + threadIdx.x; i < c.len; i += kBlock) {
-    const float uv = fmaf(mu, u[i], fmaf(wd, w[i], g[i]));
-    u[i] = uv;
-    g[i] = uv;
-  }
+  for_chunk(c.len, [&](auto width, int i) {
+    constexpr int N = decltype(width)::value;
+    Vec<N> uv = load<N>(u, i);
+    const Vec<N> gv = load<N>(g, i), wv = load<N>(w, i);
+#pragma unroll
+    for (int j = 0; j < N; ++j) uv[j] = fmaf(mu, uv[j], fmaf(wd, wv[j], gv[j]));
+    store<N>(u, i, uv);
+    store<N>(g, i, uv);
+  });
 }
 
 // Momentum factor masking: u[idx] = 0 for every index this rank sent.
@@ -428,17 +401,11 @@ __global__ __launch_bounds__(kBlock) void segmented_sumsq_kernel(const float* __
   const float* wp = w + c.start;
   const float* gp = g + c.start;
   float sw = 0.f, sg = 0.f;
-  const int n4 = c.len >> 2;
-  for (int i = threadIdx.x; i < n4; i += kBlock) {
-    const float4 a = reinterpret_cast<const float4*>(wp)[i];
-    const float4 b = reinterpret_cast<const float4*>(gp)[i];
-    sw += (a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w);
-    sg += (b.x * b.x + b.y * b.y) + (b.z * b.z + b.w * b.w);
-  }
-  for (int i = (n4 << 2) + threadIdx.x; i < c.len; i += kBlock) {
-    sw += wp[i] * wp[i];
-    sg += gp[i] * gp[i];
-  }
+  for_chunk(c.len, [&](auto width, int i) {
+    constexpr int N = decltype(width)::value;
+    sw += sumsq<N>(load<N>(wp, i));
+    sg += sumsq<N>(load<N>(gp, i));
+  });
   __shared__ double sh[kWavesPerBlock];
   const double bw = block_sum((double)sw, sh);
   const double bg = block_sum((double)sg, sh);
@@ -468,23 +435,15 @@ __global__ __launch_bounds__(kBlock) void fused_lars_kernel(LarsArgs a) {
   float* w = a.w + c.start;
   float* m = a.m + c.start;
   const float* g = a.g + c.start;
-  const int n4 = c.len >> 2;
-  for (int i = threadIdx.x; i < n4; i += kBlock) {
-    float4 wv = reinterpret_cast<float4*>(w)[i];
-    float4 mv = reinterpret_cast<float4*>(m)[i];
-    const float4 gv = reinterpret_cast<const float4*>(g)[i];
-    wv.x = lars_elem(wv.x, mv.x, gv.x, wd, mom, slr);
-    wv.y = lars_elem(wv.y, mv.y, gv.y, wd, mom, slr);
-    wv.z = lars_elem(wv.z, mv.z, gv.z, wd, mom, slr);
-    wv.w = lars_elem(wv.w, mv.w, gv.w, wd, mom, slr);
-    reinterpret_cast<float4*>(w)[i] = wv;
-    reinterpret_cast<float4*>(m)[i] = mv;
-  }
-  for (int i = (n4 << 2) + threadIdx.x; i < c.len; i += kBlock) {
-    float mv = m[i];
-    w[i] = lars_elem(w[i], mv, g[i], wd, mom, slr);
-    m[i] = mv;
-  }
+  for_chunk(c.len, [&](auto width, int i) {
+    constexpr int N = decltype(width)::value;
+    Vec<N> wv = load<N>(w, i), mv = load<N>(m, i);
+    const Vec<N> gv = load<N>(g, i);
+#pragma unroll
+    for (int j = 0; j < N; ++j) wv[j] = lars_elem(wv[j], mv[j], gv[j], wd, mom, slr);
+    store<N>(w, i, wv);
+    store<N>(m, i, mv);
+  });
 }
 
 // ---- global-norm clip -------------------------------------------------------
