@@ -7,6 +7,7 @@
 | mnist     | 1x28x28 (32x32 for lenet) | 10      | 60,000        |
 | ptb       | 35 tokens         | 10,000          | 929,589 tokens|
 | wikipedia | 512 tokens (MLM)  | 30,522          | 1,000,000     |
+| openwebtext | 1024 tokens (causal LM, batch first) | 50,304 | 8,800,000 |
 
 ``learnable=True`` makes labels a fixed function of the inputs (argmax of a
 random projection / next-token shift) so convergence tests see the loss fall.
@@ -28,7 +29,7 @@ class DatasetSpec:
     num_classes: int
     train_samples: int
     test_samples: int
-    kind: str  # image | tokens | mlm
+    kind: str  # image | tokens | mlm | speech | causal_lm
 
 
 DATASETS = {
@@ -38,6 +39,8 @@ DATASETS = {
     "mnist32": DatasetSpec("mnist32", (1, 32, 32), 10, 60000, 10000, "image"),
     "ptb": DatasetSpec("ptb", (35,), 10000, 929589, 82430, "tokens"),
     "wikipedia": DatasetSpec("wikipedia", (512,), 30522, 1000000, 10000, "mlm"),
+    # GPT-2's corpus in 1024-token sequences (about 9B tokens), vocabulary padded to a multiple of 64
+    "openwebtext": DatasetSpec("openwebtext", (1024,), 50304, 8800000, 10000, "causal_lm"),
     # AN4 spectrograms: 161 frequency bins x ~2 s of 10 ms frames, 29 characters (CTC blank = 0)
     "an4": DatasetSpec("an4", (1, 161, 200), 29, 948, 130, "speech"),
 }
@@ -100,6 +103,16 @@ class SyntheticData:
             else:
                 seq = torch.randint(0, self.vocab, (T + 1, B), generator=g)
             return seq[:-1].to(self.device), seq[1:].to(self.device)
+        if s.kind == "causal_lm":
+            # batch-first [B, T] ids and their next-token labels (the "tokens" kind is time-first, for the LSTM);
+            # learnable: the same counting sequences
+            T = self.seq_len
+            if self.learnable:
+                start = torch.randint(0, self.vocab, (B, 1), generator=g)
+                seq = (start + torch.arange(T + 1).unsqueeze(0)) % self.vocab
+            else:
+                seq = torch.randint(0, self.vocab, (B, T + 1), generator=g)
+            return seq[:, :-1].contiguous().to(self.device), seq[:, 1:].contiguous().to(self.device)
         # masked LM, Google-BERT pre-training format: a fixed number of masked
         # positions per sequence (max_predictions_per_seq = 15% of T rounded up
         # to 8: 80 at T = 512, 20 at T = 128) with their labels, so the MLM

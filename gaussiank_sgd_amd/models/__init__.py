@@ -12,6 +12,7 @@ from typing import Callable, Dict, Tuple
 import torch.nn as nn
 
 from .bert import BertForMaskedLM, MaskedLMLoss, bert_base, bert_tiny
+from .gpt import CausalLMLoss, GPTForCausalLM, gpt2, gpt_tiny
 from .lstm_ptb import PTBLSTM, lstm, repackage_hidden
 from .mlp import FCN5Net, LeNet, LinearRegression, MnistNet
 from .resnet_cifar import (CifarPreResNet, CifarResNet, preresnet20, preresnet56, preresnet110, resnet20, resnet32,
@@ -49,6 +50,8 @@ _REGISTRY: Dict[str, Tuple[Callable[..., nn.Module], str]] = {
                                    num_steps=kw.get("num_steps", 35)), "ptb"),
     "bert": (lambda nc, **kw: bert_base(), "wikipedia"),
     "bert_tiny": (lambda nc, **kw: bert_tiny(), "wikipedia"),
+    "gpt2": (lambda nc, **kw: gpt2(), "openwebtext"),
+    "gpt_tiny": (lambda nc, **kw: gpt_tiny(), "openwebtext"),
 }
 
 

@@ -23,8 +23,19 @@ backward's ``delta``, which short sequences need (few keys, concentrated
 probabilities).  A sequence
 without any valid key gives zeros (output and gradients) where SDPA gives NaN.
 
+``causal=True`` is the lower-triangular mask of a decoder: query ``q`` sees key
+``k`` iff ``k <= q``, ANDed with ``key_mask`` when both are given.  The kernels
+take it as a compile-time variant (a Python bool here, so a captured step
+replays it): key tiles past a workgroup's last query are never visited, tiles
+below the diagonal carry no mask work, and only the diagonal tiles are masked
+element by element.  A query without a visible valid key (left padding, a hole
+over keys ``0 .. q``) gives output 0, zero dQ and adds nothing to dK / dV, where
+SDPA gives NaN.  The causal bf16 forward keeps ``out_lo`` too, with or without
+a key mask: the first rows of a sequence see few keys.
+
 Elsewhere (CPU, ``attn_mask``, other head dims) it is
-``F.scaled_dot_product_attention`` with identical semantics.
+``F.scaled_dot_product_attention`` with identical semantics (``is_causal``, or
+the lower triangle merged into the mask).
 
 Not in the reference (its model zoo has no transformer); BASELINE config 5
 (BERT-base MLM) runs it.
@@ -125,10 +136,16 @@ def merge_masks(attn_mask, key_mask, B: int, T: int):
     return attn_mask.masked_fill(~km, float("-inf"))
 
 
+def causal_mask(T: int, device) -> torch.Tensor:
+    """bool ``[T, T]``, True where query (row) sees key (column): ``k <= q``."""
+    return torch.ones(T, T, dtype=torch.bool, device=device).tril_()
+
+
 def reference_attention(qkv: torch.Tensor, heads: int, p: float = 0.0, seed: int = 0,
-                        key_mask=None) -> torch.Tensor:
+                        key_mask=None, causal: bool = False) -> torch.Tensor:
     """fp32 composition with the kernels' exact dropout mask (autograd-able);
-    ``key_mask``: masked keys score -inf."""
+    ``key_mask``: masked keys score -inf; ``causal``: so do keys after the
+    query.  A row without a visible valid key gives zeros, not NaN."""
     B, T, H3 = qkv.shape
     d = H3 // (3 * heads)
     x = qkv.float().view(B, T, 3, heads, d)
@@ -136,7 +153,16 @@ def reference_attention(qkv: torch.Tensor, heads: int, p: float = 0.0, seed: int
     s = torch.matmul(q, k.transpose(-1, -2)) / d ** 0.5
     if key_mask is not None:
         s = s.masked_fill(~key_mask_bool(key_mask, B, T)[:, None, None, :], float("-inf"))
-    a = torch.softmax(s, dim=-1)
+    if causal:
+        s = s.masked_fill(~causal_mask(T, s.device), float("-inf"))
+        if key_mask is not None:
+            # rows that see nothing: a finite score row (so that softmax and its gradient stay finite), zeroed after
+            dark = torch.isinf(s).all(dim=-1, keepdim=True)
+            a = torch.softmax(s.masked_fill(dark, 0.0), dim=-1).masked_fill(dark, 0.0)
+        else:
+            a = torch.softmax(s, dim=-1)
+    else:
+        a = torch.softmax(s, dim=-1)
     if p > 0:
         keep = dropout_mask(B, heads, T, p, seed, qkv.device)
         a = a * keep.to(a.dtype) * drop_scale(p)
@@ -146,19 +172,22 @@ def reference_attention(qkv: torch.Tensor, heads: int, p: float = 0.0, seed: int
 
 class _FlashAttnFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, heads, p, seed, seed_dev=None, key_bits=None):
+    def forward(ctx, qkv, heads, p, seed, seed_dev=None, key_bits=None, causal=False):
         # seed_dev: the graph replay word (ops.graph_seed_word) under capture --
         # forward and backward of one replay read the same word
         # key_bits: the packed key mask (pack_key_mask), shared with the backward
+        # causal: a Python bool, it picks the kernels' CAUSAL instantiations
         B, T, _ = qkv.shape
         out = torch.empty(B, T, heads * HEAD_DIM, dtype=torch.bfloat16, device=qkv.device)
         lse = torch.empty(B * heads * T, dtype=torch.float32, device=qkv.device)
         # with a mask, rows with few valid keys have concentrated probabilities, where dP and delta =
         # rowsum(dO * O) nearly cancel: the forward also keeps what the bf16 rounding of O dropped
-        out_lo = None if key_bits is None else torch.empty_like(out)
-        _ops().attn_fwd(qkv, out, lse, int(heads), float(p), int(seed), seed_dev, key_bits, out_lo)
+        # (causal: the first rows of a sequence are such rows)
+        out_lo = None if key_bits is None and not causal else torch.empty_like(out)
+        _ops().attn_fwd(qkv, out, lse, int(heads), float(p), int(seed), seed_dev, key_bits, out_lo, bool(causal))
         ctx.save_for_backward(qkv, out, lse, key_bits, out_lo)
         ctx.heads, ctx.p, ctx.seed, ctx.seed_dev = int(heads), float(p), int(seed), seed_dev
+        ctx.causal = bool(causal)
         return out
 
     @staticmethod
@@ -167,8 +196,9 @@ class _FlashAttnFn(torch.autograd.Function):
         dout = dout.to(torch.bfloat16).contiguous()
         delta = torch.empty_like(lse)
         dqkv = torch.empty_like(qkv)
-        _ops().attn_bwd(qkv, out, dout, lse, delta, dqkv, ctx.heads, ctx.p, ctx.seed, ctx.seed_dev, key_bits, out_lo)
-        return dqkv, None, None, None, None, None
+        _ops().attn_bwd(qkv, out, dout, lse, delta, dqkv, ctx.heads, ctx.p, ctx.seed, ctx.seed_dev, key_bits, out_lo,
+                        ctx.causal)
+        return dqkv, None, None, None, None, None, None
 
 
 class _FlashAttnF32Fn(torch.autograd.Function):
@@ -176,13 +206,14 @@ class _FlashAttnF32Fn(torch.autograd.Function):
     v_mfma_f32_16x16x4_f32, the same dropout hashes."""
 
     @staticmethod
-    def forward(ctx, qkv, heads, p, seed, seed_dev=None, key_bits=None):
+    def forward(ctx, qkv, heads, p, seed, seed_dev=None, key_bits=None, causal=False):
         B, T, _ = qkv.shape
         out = torch.empty(B, T, heads * HEAD_DIM, dtype=torch.float32, device=qkv.device)
         lse = torch.empty(B * heads * T, dtype=torch.float32, device=qkv.device)
-        _ops().attn_f32_fwd(qkv, out, lse, int(heads), float(p), int(seed), seed_dev, key_bits)
+        _ops().attn_f32_fwd(qkv, out, lse, int(heads), float(p), int(seed), seed_dev, key_bits, bool(causal))
         ctx.save_for_backward(qkv, out, lse, key_bits)
         ctx.heads, ctx.p, ctx.seed, ctx.seed_dev = int(heads), float(p), int(seed), seed_dev
+        ctx.causal = bool(causal)
         return out
 
     @staticmethod
@@ -191,8 +222,9 @@ class _FlashAttnF32Fn(torch.autograd.Function):
         dout = dout.to(torch.float32).contiguous()
         delta = torch.empty_like(lse)
         dqkv = torch.empty_like(qkv)
-        _ops().attn_f32_bwd(qkv, out, dout, lse, delta, dqkv, ctx.heads, ctx.p, ctx.seed, ctx.seed_dev, key_bits)
-        return dqkv, None, None, None, None, None
+        _ops().attn_f32_bwd(qkv, out, dout, lse, delta, dqkv, ctx.heads, ctx.p, ctx.seed, ctx.seed_dev, key_bits,
+                            ctx.causal)
+        return dqkv, None, None, None, None, None, None
 
 
 def _compute_dtype(qkv: torch.Tensor):
@@ -231,18 +263,33 @@ def fused_available_for(x: torch.Tensor, T: int, heads: int, width: int) -> bool
     return _kernels_take(x, T, heads, width)
 
 
-def _sdpa(qkv: torch.Tensor, heads: int, p: float, attn_mask=None) -> torch.Tensor:
+def merge_causal(attn_mask, T: int, device):
+    """``attn_mask`` (bool or additive, or None) with the lower triangle merged in."""
+    tri = causal_mask(T, device)
+    if attn_mask is None:
+        return tri
+    if attn_mask.dtype == torch.bool:
+        return attn_mask & tri
+    return attn_mask.masked_fill(~tri, float("-inf"))
+
+
+def _sdpa(qkv: torch.Tensor, heads: int, p: float, attn_mask=None, causal: bool = False) -> torch.Tensor:
     B, T, H3 = qkv.shape
     d = H3 // (3 * heads)
     x = qkv.view(B, T, 3, heads, d)
     q, k, v = (x[:, :, i].transpose(1, 2) for i in range(3))
-    o = F.scaled_dot_product_attention(q, k, v, attn_mask=attn_mask, dropout_p=p)
+    if causal and attn_mask is not None:   # SDPA takes is_causal or a mask, not both
+        attn_mask, causal = merge_causal(attn_mask, T, qkv.device), False
+    o = F.scaled_dot_product_attention(q, k, v, attn_mask=attn_mask, dropout_p=p, is_causal=causal)
     return o.transpose(1, 2).reshape(B, T, heads * d)
 
 
 def self_attention(qkv: torch.Tensor, heads: int, p: float = 0.0, training: bool = True,
-                   attn_mask=None, seed: int = None, key_mask=None) -> torch.Tensor:
+                   attn_mask=None, seed: int = None, key_mask=None, causal: bool = False) -> torch.Tensor:
     """``[B, T, 3*heads*d]`` packed projection -> ``[B, T, heads*d]`` attention output.
+    ``causal``: query ``q`` sees keys ``k <= q`` only (ANDed with ``key_mask``);
+    the fused kernels take it (and then keep ``out_lo``, as with a key mask).  On
+    the SDPA path a query without a visible valid key gives NaN, in the kernels 0.
     ``key_mask``: a key-padding mask, ``[B, T]`` (nonzero = valid) or packed
     (``pack_key_mask``); the fused kernels take it, ``attn_mask`` forces SDPA.
     An all-valid mask gives the unmasked call's output bit for bit; its bf16
@@ -257,6 +304,6 @@ def self_attention(qkv: torch.Tensor, heads: int, p: float = 0.0, training: bool
         seed_dev = capture_seed_word(qkv.device) if p > 0 else None
         bits = None if key_mask is None else _key_bits(key_mask, B, T)   # packed once, kept for the backward
         if _compute_dtype(qkv) == torch.float32:
-            return _FlashAttnF32Fn.apply(qkv.contiguous(), heads, p, seed, seed_dev, bits)
-        return _FlashAttnFn.apply(qkv.to(torch.bfloat16).contiguous(), heads, p, seed, seed_dev, bits)
-    return _sdpa(qkv, heads, p, merge_masks(attn_mask, key_mask, B, T))
+            return _FlashAttnF32Fn.apply(qkv.contiguous(), heads, p, seed, seed_dev, bits, bool(causal))
+        return _FlashAttnFn.apply(qkv.to(torch.bfloat16).contiguous(), heads, p, seed, seed_dev, bits, bool(causal))
+    return _sdpa(qkv, heads, p, merge_masks(attn_mask, key_mask, B, T), bool(causal))

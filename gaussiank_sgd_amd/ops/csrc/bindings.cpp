@@ -1844,17 +1844,18 @@ const uint32_t* key_bits_ptr(const c10::optional<at::Tensor>& t, const at::Tenso
   return reinterpret_cast<const uint32_t*>(t->data_ptr<int32_t>());
 }
 
-// the output's rounding residue (bf16, with key_bits only); null when absent
-void* out_lo_ptr(const c10::optional<at::Tensor>& t, const uint32_t* key_bits, int64_t rows, int64_t cols) {
+// the output's rounding residue (bf16, with key_bits or causal only); null when absent
+void* out_lo_ptr(const c10::optional<at::Tensor>& t, const uint32_t* key_bits, bool causal, int64_t rows,
+                 int64_t cols) {
   if (!t.has_value() || !t->defined()) return nullptr;
-  TORCH_CHECK(key_bits != nullptr, "out_lo needs key_bits (only the masked kernels take it)");
+  TORCH_CHECK(key_bits != nullptr || causal, "out_lo needs key_bits or causal (only the masked kernels take it)");
   check_attn(*t, "out_lo", rows, cols);
   return t->data_ptr();
 }
 
 void attn_fwd(at::Tensor qkv, at::Tensor out, at::Tensor lse, int64_t heads, double p, int64_t seed,
               c10::optional<at::Tensor> seed_dev, c10::optional<at::Tensor> key_bits,
-              c10::optional<at::Tensor> out_lo) {
+              c10::optional<at::Tensor> out_lo, bool causal) {
   TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == 3 * heads * 64, "qkv: [B, T, 3 * heads * 64]");
   const int64_t B = qkv.size(0), T = qkv.size(1);
   TORCH_CHECK(gk::attn_supported((int)T, 64), "attn: T must be a multiple of 128");
@@ -1865,12 +1866,13 @@ void attn_fwd(at::Tensor qkv, at::Tensor out, at::Tensor lse, int64_t heads, dou
   const uint32_t* kb = key_bits_ptr(key_bits, qkv, B, T);
   c10::DeviceGuard guard(qkv.device());
   gk::attn_fwd(qkv.data_ptr(), out.data_ptr(), lse.data_ptr<float>(), (int)B, (int)T, (int)heads, (float)p,
-               (uint32_t)seed, seed_word(seed_dev), kb, out_lo_ptr(out_lo, kb, B * T, heads * 64), cur_stream(qkv));
+               (uint32_t)seed, seed_word(seed_dev), kb, out_lo_ptr(out_lo, kb, causal, B * T, heads * 64), causal,
+               cur_stream(qkv));
 }
 
 void attn_bwd(at::Tensor qkv, at::Tensor out, at::Tensor dout, at::Tensor lse, at::Tensor delta, at::Tensor dqkv,
               int64_t heads, double p, int64_t seed, c10::optional<at::Tensor> seed_dev,
-              c10::optional<at::Tensor> key_bits, c10::optional<at::Tensor> out_lo) {
+              c10::optional<at::Tensor> key_bits, c10::optional<at::Tensor> out_lo, bool causal) {
   TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == 3 * heads * 64, "qkv: [B, T, 3 * heads * 64]");
   const int64_t B = qkv.size(0), T = qkv.size(1);
   TORCH_CHECK(gk::attn_supported((int)T, 64), "attn: T must be a multiple of 128");
@@ -1884,7 +1886,7 @@ void attn_bwd(at::Tensor qkv, at::Tensor out, at::Tensor dout, at::Tensor lse, a
   c10::DeviceGuard guard(qkv.device());
   gk::attn_bwd(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr<float>(), delta.data_ptr<float>(),
                dqkv.data_ptr(), (int)B, (int)T, (int)heads, (float)p, (uint32_t)seed, seed_word(seed_dev), kb,
-               out_lo_ptr(out_lo, kb, B * T, heads * 64), cur_stream(qkv));
+               out_lo_ptr(out_lo, kb, causal, B * T, heads * 64), causal, cur_stream(qkv));
 }
 
 void check_attn32(const at::Tensor& t, const char* name, int64_t rows, int64_t cols) {
@@ -1894,7 +1896,7 @@ void check_attn32(const at::Tensor& t, const char* name, int64_t rows, int64_t c
 }
 
 void attn_f32_fwd(at::Tensor qkv, at::Tensor out, at::Tensor lse, int64_t heads, double p, int64_t seed,
-                  c10::optional<at::Tensor> seed_dev, c10::optional<at::Tensor> key_bits) {
+                  c10::optional<at::Tensor> seed_dev, c10::optional<at::Tensor> key_bits, bool causal) {
   TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == 3 * heads * 64, "qkv: [B, T, 3 * heads * 64]");
   const int64_t B = qkv.size(0), T = qkv.size(1);
   TORCH_CHECK(gk::attn_f32_supported((int)T, 64), "attn_f32: T must be a multiple of 128");
@@ -1906,12 +1908,12 @@ void attn_f32_fwd(at::Tensor qkv, at::Tensor out, at::Tensor lse, int64_t heads,
   const uint32_t* kb = key_bits_ptr(key_bits, qkv, B, T);
   c10::DeviceGuard guard(qkv.device());
   gk::attn_f32_fwd(qkv.data_ptr<float>(), out.data_ptr<float>(), lse.data_ptr<float>(), (int)B, (int)T, (int)heads,
-                   (float)p, (uint32_t)seed, seed_word(seed_dev), kb, cur_stream(qkv));
+                   (float)p, (uint32_t)seed, seed_word(seed_dev), kb, causal, cur_stream(qkv));
 }
 
 void attn_f32_bwd(at::Tensor qkv, at::Tensor out, at::Tensor dout, at::Tensor lse, at::Tensor delta, at::Tensor dqkv,
                   int64_t heads, double p, int64_t seed, c10::optional<at::Tensor> seed_dev,
-                  c10::optional<at::Tensor> key_bits) {
+                  c10::optional<at::Tensor> key_bits, bool causal) {
   TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == 3 * heads * 64, "qkv: [B, T, 3 * heads * 64]");
   const int64_t B = qkv.size(0), T = qkv.size(1);
   TORCH_CHECK(gk::attn_f32_supported((int)T, 64), "attn_f32: T must be a multiple of 128");
@@ -1925,7 +1927,7 @@ void attn_f32_bwd(at::Tensor qkv, at::Tensor out, at::Tensor dout, at::Tensor ls
   c10::DeviceGuard guard(qkv.device());
   gk::attn_f32_bwd(qkv.data_ptr<float>(), out.data_ptr<float>(), dout.data_ptr<float>(), lse.data_ptr<float>(),
                    delta.data_ptr<float>(), dqkv.data_ptr<float>(), (int)B, (int)T, (int)heads, (float)p,
-                   (uint32_t)seed, seed_word(seed_dev), kb, cur_stream(qkv));
+                   (uint32_t)seed, seed_word(seed_dev), kb, causal, cur_stream(qkv));
 }
 
 // [B, T] key mask (nonzero = valid; any 1-, 2-, 4- or 8-byte dtype) -> packed bits int32 [B, T / 32]
@@ -2263,15 +2265,16 @@ TORCH_LIBRARY(gksgd, m) {
   m.def("attn_supported(int T, int D) -> bool",
         [](int64_t T, int64_t D) { return gk::attn_supported((int)T, (int)D); });
   m.def("attn_fwd(Tensor qkv, Tensor(a!) out, Tensor(b!) lse, int heads, float p, int seed, Tensor? seed_dev=None, "
-        "Tensor? key_bits=None, Tensor(c!)? out_lo=None) -> ()");
+        "Tensor? key_bits=None, Tensor(c!)? out_lo=None, bool causal=False) -> ()");
   m.def("attn_pack_key_mask(Tensor mask, Tensor(a!) bits) -> ()");
   m.def("attn_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, Tensor(a!) delta, Tensor(b!) dqkv, int heads, "
-        "float p, int seed, Tensor? seed_dev=None, Tensor? key_bits=None, Tensor? out_lo=None) -> ()");
+        "float p, int seed, Tensor? seed_dev=None, Tensor? key_bits=None, Tensor? out_lo=None, "
+        "bool causal=False) -> ()");
   m.def("attn_dropout_mask(Tensor(a!) mask, int B, int heads, int T, float p, int seed, Tensor? seed_dev=None) -> ()");
   m.def("attn_f32_fwd(Tensor qkv, Tensor(a!) out, Tensor(b!) lse, int heads, float p, int seed, Tensor? seed_dev=None, "
-        "Tensor? key_bits=None) -> ()");
+        "Tensor? key_bits=None, bool causal=False) -> ()");
   m.def("attn_f32_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, Tensor(a!) delta, Tensor(b!) dqkv, int heads, "
-        "float p, int seed, Tensor? seed_dev=None, Tensor? key_bits=None) -> ()");
+        "float p, int seed, Tensor? seed_dev=None, Tensor? key_bits=None, bool causal=False) -> ()");
   m.def("attn_f32_supported(int T, int D) -> bool",
         [](int64_t T, int64_t D) { return gk::attn_f32_supported((int)T, (int)D); });
   m.def("add_ln_supported(int H) -> bool", &add_ln_supported);

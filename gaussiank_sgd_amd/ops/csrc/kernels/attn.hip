@@ -54,6 +54,22 @@
 // (out_lo), which the dQ kernel adds back for delta = rowsum(dO * O): rows
 // with few valid keys have concentrated P, where dP and delta nearly cancel.
 // The MASK = false instantiations are the code without any of this.
+//
+// Causal mask (CAUSAL instantiations): query q sees key k iff k <= q, ANDed
+// with the key bits under MASK.  The forward and the dQ kernel stop at tile
+// 2 qb + 2 (the last one their query 128 qb + 127 sees); per wave a tile is
+// fully visible (no mask work), diagonal (masked element-wise through the
+// accumulator init, attn_mask.h) or past the wave's last query (waves 0 and 1
+// on the workgroup's last tile: arithmetic skipped, barrier and staging kept).
+// The dK/dV kernel starts its query tiles at 2 kb; waves 2 and 3 skip the
+// arithmetic of that tile.  Every case is wave-uniform.  The forward's lazy
+// running max is then kept per row: a row below the threshold does not move
+// its m when another row of the wave does, so nothing a later query sees
+// changes an earlier row's bits, and under MASK a row whose scores have all
+// been -inf so far (left padding) waits for its first finite one; a query
+// without any visible valid key gives out = 0, lse = 0 and zero dQ.  out_lo is
+// kept as under MASK: the first rows of a sequence see few keys.
+// The CAUSAL = false instantiations are the code without any of this.
 #include "common.h"
 #include "gk_kernels.h"
 #include "mfma_util.h"
@@ -223,15 +239,22 @@ __device__ __forceinline__ uint32_t eff_seed(const AttnArgs& a) {
 // tiles of 64 keys in a 3-deep LDS ring
 // ---------------------------------------------------------------------------
 // (MASK: held to the 3 workgroups per CU that the unmasked forward's register count already allows)
-template <bool DROP, bool MASK>
-__global__ void __launch_bounds__(64 * kAW, MASK ? 3 : 2) attn_fwd_kernel(AttnArgs a) {
+template <bool DROP, bool MASK, bool CAUSAL = false>
+__global__ void __launch_bounds__(64 * kAW, (MASK || CAUSAL) ? 3 : 2) attn_fwd_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(1024))) char smem[kStages * 2 * kTileB];
   const uint32_t seed = DROP ? eff_seed(a) : 0u;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, g = lane >> 4;
   const int T = a.T, H = a.H;
   const int nqb = T / kRows;
-  const int blk = xcd_block();
-  const int bh = blk / nqb, qb = blk - bh * nqb;
+  int bh, qb;
+  if constexpr (CAUSAL) {   // heaviest row blocks first (attn_mask.h)
+    causal_block(nqb, bh, qb);
+    qb = nqb - 1 - qb;
+  } else {
+    const int blk = xcd_block();
+    bh = blk / nqb;
+    qb = blk - bh * nqb;
+  }
   const int b = bh / H, h = bh - b * H;
   const uint32_t* kbits = MASK ? a.key_bits + (int64_t)b * (T >> 5) : nullptr;
   const int64_t ld = 3LL * H * kHD;
@@ -242,7 +265,10 @@ __global__ void __launch_bounds__(64 * kAW, MASK ? 3 : 2) attn_fwd_kernel(AttnAr
   dma.init(base + (int64_t)(H + h) * kHD, ld, base + (int64_t)(2 * H + h) * kHD, ld, wave, lane);
   const int64_t tstep = kKT * ld;
   // MASK: stop after the last tile with a valid key (0 tiles: an empty sequence)
-  const int nt = MASK ? mask_tiles(kbits, T >> 5, lane) : T / kKT;
+  const int ntm = MASK ? mask_tiles(kbits, T >> 5, lane) : T / kKT;
+  // CAUSAL: and after the workgroup's last visible tile, the one of its query 128 qb + 127
+  const int nt = CAUSAL ? min(ntm, 2 * qb + 2) : ntm;
+  const int q0u = CAUSAL ? __builtin_amdgcn_readfirstlane(q0) : 0;   // wave-uniform: the tile cases below
 
   bf16x8 qf[2][2];
 #pragma unroll
@@ -273,6 +299,10 @@ __global__ void __launch_bounds__(64 * kAW, MASK ? 3 : 2) attn_fwd_kernel(AttnAr
 
   int cur = 0, pre = 2;   // ring slots of tile t and of tile t + 2
   bool started = false;   // MASK: a tile with a valid key has been seen
+  // CAUSAL && MASK: the row has had no finite score yet.  Left padding or a hole over keys 0 .. q leaves a
+  // row's first tiles all -inf; such a row does not move m and takes the first-tile step at its first
+  // finite score (a row that never has one ends with l = 0: out = 0, lse = 0)
+  bool fresh[2] = {true, true};
   for (int t = 0; t < nt; ++t) {
     uint32_t w0 = ~0u, w1 = ~0u;   // valid bits of the tile's 64 keys (workgroup-uniform)
     if (MASK) {
@@ -283,7 +313,12 @@ __global__ void __launch_bounds__(64 * kAW, MASK ? 3 : 2) attn_fwd_kernel(AttnAr
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     if (t + 2 < nt) dma.issue((t + 2) * tstep, (t + 2) * tstep, lds + pre * 2 * kTileB, wave);
-    if (MASK && (w0 | w1) == 0u) {   // no valid key: the ring moves on, the arithmetic is skipped
+    // CAUSAL, per wave: the tile is fully visible (qrel >= 63), diagonal, or past the wave's last query
+    // (qrel < -31: waves 0 and 1 on the workgroup's last tile)
+    const int qrel = CAUSAL ? q0u - kKT * t : 0;
+    // no valid / no visible key: the ring moves on, the arithmetic is skipped (the wave has passed the
+    // tile's barrier and staged its pieces)
+    if ((MASK && (w0 | w1) == 0u) || (CAUSAL && qrel < -31)) {
       cur = ring_next(cur);
       pre = ring_next(pre);
       continue;
@@ -294,12 +329,13 @@ __global__ void __launch_bounds__(64 * kAW, MASK ? 3 : 2) attn_fwd_kernel(AttnAr
     // -inf for a masked key, which the MFMA carries through; set before the
     // operand reads so that the tile's arithmetic stays one scheduling region)
     f32x4 s[2][4];
-    if (MASK) {
+    if (MASK || CAUSAL) {
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
         for (int kt = 0; kt < 4; ++kt) s[qt][kt] = splat4(-m[qt]);
-      if ((w0 & w1) != ~0u) mask_scores_t(s, w0 >> (4 * g), w1 >> (4 * g));
+      if (MASK && (w0 & w1) != ~0u) mask_scores_t(s, w0 >> (4 * g), w1 >> (4 * g));
+      if (CAUSAL && qrel < 63) causal_scores_t(s, qrel + li - 4 * g);
     }
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt) {
@@ -307,9 +343,10 @@ __global__ void __launch_bounds__(64 * kAW, MASK ? 3 : 2) attn_fwd_kernel(AttnAr
       const bf16x8 k1 = *reinterpret_cast<const bf16x8*>(Ks + aoff(16 * kt + li, 4 + g));
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt)
-        s[qt][kt] = mfma(k1, qf[qt][1], mfma(k0, qf[qt][0], MASK ? s[qt][kt] : splat4(-m[qt])));
+        s[qt][kt] = mfma(k1, qf[qt][1], mfma(k0, qf[qt][0], (MASK || CAUSAL) ? s[qt][kt] : splat4(-m[qt])));
     }
-    // the first tile (MASK: the first with a valid key, where every row has a finite max)
+    // the first tile (MASK: the first with a valid key, where every row has a finite max; CAUSAL alone:
+    // tile 0, key 0 is visible to every query; CAUSAL && MASK: per row, fresh[])
     const bool first = MASK ? !started : t == 0;
     started = true;
 
@@ -319,10 +356,21 @@ __global__ void __launch_bounds__(64 * kAW, MASK ? 3 : 2) attn_fwd_kernel(AttnAr
 #pragma unroll
       for (int kt = 1; kt < 4; ++kt)
         mx = fmaxf(mx, fmaxf(fmaxf(s[qt][kt][0], s[qt][kt][1]), fmaxf(s[qt][kt][2], s[qt][kt][3])));
-      if (first || __ballot(mx > kLazy) != 0) {   // wave-uniform, rare after the first tile
+      // wave-uniform, rare after the first tile
+      if ((CAUSAL && MASK) ? __ballot(fresh[qt] || mx > kLazy) != 0 : first || __ballot(mx > kLazy) != 0) {
         mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float d = first ? mx : fmaxf(mx, 0.f);
+        float d;
+        if constexpr (CAUSAL) {
+          // per row: a row below the threshold keeps its m bit for bit (d = 0 changes nothing), so what
+          // another row of the wave scores -- a later query sees keys this one does not -- cannot reach it
+          const bool fr = MASK ? fresh[qt] : first;
+          const bool dark = MASK && mx == -INFINITY;   // no finite score in this tile
+          d = fr ? (dark ? 0.f : mx) : (mx > kLazy ? mx : 0.f);
+          if (MASK) fresh[qt] = fr && dark;
+        } else {
+          d = first ? mx : fmaxf(mx, 0.f);
+        }
         m[qt] += d;
         const float al = fexp2(-d);
         l[qt] *= al;
@@ -394,7 +442,7 @@ __global__ void __launch_bounds__(64 * kAW, MASK ? 3 : 2) attn_fwd_kernel(AttnAr
     uint16_t* op = a.o + ((int64_t)b * T + q) * (H * kHD) + h * kHD + 4 * g;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) store4(op + 16 * dt, o[qt][dt], inv);
-    if (MASK && a.out_lo != nullptr) {
+    if ((MASK || CAUSAL) && a.out_lo != nullptr) {
       uint16_t* lp = a.out_lo + ((int64_t)b * T + q) * (H * kHD) + h * kHD + 4 * g;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) store4_lo(lp + 16 * dt, o[qt][dt], inv);
@@ -407,15 +455,22 @@ __global__ void __launch_bounds__(64 * kAW, MASK ? 3 : 2) attn_fwd_kernel(AttnAr
 // tile S^T = c K Q^T - lse, dZ^T = V dO^T - delta', dS^T = P^T (dP^T - delta),
 // dQ^T += K^T dS^T
 // ---------------------------------------------------------------------------
-template <bool DROP, bool MASK>
+template <bool DROP, bool MASK, bool CAUSAL = false>
 __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_dq_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(1024))) char smem[kStages * 2 * kTileB];
   const uint32_t seed = DROP ? eff_seed(a) : 0u;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, g = lane >> 4;
   const int T = a.T, H = a.H;
   const int nqb = T / kRows;
-  const int blk = xcd_block();
-  const int bh = blk / nqb, qb = blk - bh * nqb;
+  int bh, qb;
+  if constexpr (CAUSAL) {   // heaviest row blocks first (attn_mask.h)
+    causal_block(nqb, bh, qb);
+    qb = nqb - 1 - qb;
+  } else {
+    const int blk = xcd_block();
+    bh = blk / nqb;
+    qb = blk - bh * nqb;
+  }
   const int b = bh / H, h = bh - b * H;
   const uint32_t* kbits = MASK ? a.key_bits + (int64_t)b * (T >> 5) : nullptr;
   const int64_t ld = 3LL * H * kHD, ldo = (int64_t)H * kHD;
@@ -426,7 +481,9 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_dq_kernel(AttnArgs a) {
   dma.init(base + (int64_t)(H + h) * kHD, ld, base + (int64_t)(2 * H + h) * kHD, ld, wave, lane);
   const int64_t tstep = kKT * ld;
   // MASK: stop after the last tile with a valid key (0 tiles: an empty sequence)
-  const int nt = MASK ? mask_tiles(kbits, T >> 5, lane) : T / kKT;
+  const int ntm = MASK ? mask_tiles(kbits, T >> 5, lane) : T / kKT;
+  const int nt = CAUSAL ? min(ntm, 2 * qb + 2) : ntm;   // CAUSAL: the forward's tile count and tile cases
+  const int q0u = CAUSAL ? __builtin_amdgcn_readfirstlane(q0) : 0;
 
   bf16x8 qf[2][2], df[2][2], of[2][2];
   // MASK: the rounding residue of the output (zero without out_lo).  With few valid keys P is concentrated,
@@ -444,7 +501,7 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_dq_kernel(AttnArgs a) {
       qf[qt][ks] = *reinterpret_cast<const bf16x8*>(base + h * kHD + (int64_t)q * ld + 32 * ks + 8 * g);
       df[qt][ks] = *reinterpret_cast<const bf16x8*>(a.dout + orow + 32 * ks + 8 * g);
       of[qt][ks] = *reinterpret_cast<const bf16x8*>(a.out + orow + 32 * ks + 8 * g);
-      if (MASK) {
+      if (MASK || CAUSAL) {
         lf[qt][ks] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
         if (a.out_lo != nullptr) lf[qt][ks] = *reinterpret_cast<const bf16x8*>(a.out_lo + orow + 32 * ks + 8 * g);
       }
@@ -462,7 +519,8 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_dq_kernel(AttnArgs a) {
       qf[qt][ks] = scale_bf16x8(qf[qt][ks], a.sc);
 #pragma unroll
       for (int j = 0; j < 8; ++j)
-        dsum = fmaf(bf2f(df[qt][ks][j]), MASK ? bf2f(of[qt][ks][j]) + bf2f(lf[qt][ks][j]) : bf2f(of[qt][ks][j]), dsum);
+        dsum = fmaf(bf2f(df[qt][ks][j]),
+                    (MASK || CAUSAL) ? bf2f(of[qt][ks][j]) + bf2f(lf[qt][ks][j]) : bf2f(of[qt][ks][j]), dsum);
     }
     dsum += __shfl_xor(dsum, 16, 64);
     dsum += __shfl_xor(dsum, 32, 64);
@@ -494,7 +552,9 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_dq_kernel(AttnArgs a) {
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     if (t + 2 < nt) dma.issue((t + 2) * tstep, (t + 2) * tstep, lds + pre * 2 * kTileB, wave);
-    if (MASK && (w0 | w1) == 0u) {   // no valid key: P = 0 for the whole tile
+    const int qrel = CAUSAL ? q0u - kKT * t : 0;   // as in the forward
+    // no valid / no visible key: P = 0 for the whole tile
+    if ((MASK && (w0 | w1) == 0u) || (CAUSAL && qrel < -31)) {
       cur = ring_next(cur);
       pre = ring_next(pre);
       continue;
@@ -503,12 +563,14 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_dq_kernel(AttnArgs a) {
     const char* Vs = Ks + kTileB;
 
     f32x4 s[2][4], dz[2][4];
-    if (MASK) {   // masked keys: -inf through the MFMA, so P = exp2(-inf) and with it dS are exactly 0
+    // masked / hidden keys: -inf through the MFMA, so P = exp2(-inf) and with it dS are exactly 0
+    if (MASK || CAUSAL) {
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
         for (int kt = 0; kt < 4; ++kt) s[qt][kt] = splat4(nlse[qt]);
-      if ((w0 & w1) != ~0u) mask_scores_t(s, w0 >> (4 * g), w1 >> (4 * g));
+      if (MASK && (w0 & w1) != ~0u) mask_scores_t(s, w0 >> (4 * g), w1 >> (4 * g));
+      if (CAUSAL && qrel < 63) causal_scores_t(s, qrel + li - 4 * g);
     }
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt) {
@@ -518,7 +580,7 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_dq_kernel(AttnArgs a) {
       const bf16x8 v1 = *reinterpret_cast<const bf16x8*>(Vs + aoff(16 * kt + li, 4 + g));
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt) {
-        s[qt][kt] = mfma(k1, qf[qt][1], mfma(k0, qf[qt][0], MASK ? s[qt][kt] : splat4(nlse[qt])));
+        s[qt][kt] = mfma(k1, qf[qt][1], mfma(k0, qf[qt][0], (MASK || CAUSAL) ? s[qt][kt] : splat4(nlse[qt])));
         dz[qt][kt] = mfma(v1, df[qt][1], mfma(v0, df[qt][0], splat4(ndel[qt])));
       }
     }
@@ -590,15 +652,21 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_dq_kernel(AttnArgs a) {
 // ---------------------------------------------------------------------------
 constexpr int kKvBuf = 2 * kTileB + 512;   // Q tile, dO tile, lse[64], delta[64]
 
-template <bool DROP, bool MASK>
+template <bool DROP, bool MASK, bool CAUSAL = false>
 __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_kv_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(1024))) char smem[kStages * kKvBuf];
   const uint32_t seed = DROP ? eff_seed(a) : 0u;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, g = lane >> 4;
   const int T = a.T, H = a.H;
   const int nkb = T / kRows;
-  const int blk = xcd_block();
-  const int bh = blk / nkb, kb = blk - bh * nkb;
+  int bh, kb;
+  if constexpr (CAUSAL) {   // heaviest key blocks (the first ones) first (attn_mask.h)
+    causal_block(nkb, bh, kb);
+  } else {
+    const int blk = xcd_block();
+    bh = blk / nkb;
+    kb = blk - bh * nkb;
+  }
   const int b = bh / H, h = bh - b * H;
   const int64_t ld = 3LL * H * kHD, ldo = (int64_t)H * kHD;
   const uint16_t* base = a.qkv + (int64_t)b * T * ld;
@@ -635,6 +703,9 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_kv_kernel(AttnArgs a) {
       __builtin_amdgcn_global_load_lds((wave ? delp : lsep) + t * kKT + lane, dst + 2 * kTileB + wave * 256, 4, 0, 0);
   };
   const int nt = T / kKT;
+  // CAUSAL: the first query tile that sees any of the workgroup's keys (nt is even, so t0 + 1 < nt)
+  const int t0 = CAUSAL ? 2 * kb : 0;
+  const int k0u = CAUSAL ? __builtin_amdgcn_readfirstlane(k0) : 0;   // wave-uniform: the tile cases below
 
   bf16x8 kf[2][2], vf[2][2];
 #pragma unroll
@@ -645,8 +716,8 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_kv_kernel(AttnArgs a) {
       kf[kt][ks] = *reinterpret_cast<const bf16x8*>(base + (int64_t)(H + h) * kHD + row);
       vf[kt][ks] = *reinterpret_cast<const bf16x8*>(base + (int64_t)(2 * H + h) * kHD + row);
     }
-  stage(0, 0);
-  if (nt > 1) stage(1, 1);
+  stage(t0, 0);
+  if (t0 + 1 < nt) stage(t0 + 1, 1);
 #pragma unroll
   for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
@@ -667,7 +738,7 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_kv_kernel(AttnArgs a) {
   const int rown = 2 * (li & 1);
 
   int cur = 0, pre = 2;   // ring slots of tile t and of tile t + 2
-  for (int t = 0; t < nt; ++t) {
+  for (int t = t0; t < nt; ++t) {
     if (wave < 2) wait_tile<kPieces + 1>(t + 1 >= nt);   // waves 0 / 1 also stage lse / delta
     else wait_tile<kPieces>(t + 1 >= nt);
     __builtin_amdgcn_s_barrier();
@@ -680,6 +751,11 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_kv_kernel(AttnArgs a) {
     cur = ring_next(cur);
     pre = ring_next(pre);
     if (MASK && ww == 0u) continue;   // no valid key in this wave: dK = dV = 0, only barriers and staging
+    // CAUSAL, per wave: krel = (tile's first query) - (wave's first key).  krel < -63: no query of the tile
+    // sees a key of the wave (waves 2 and 3 on tile 2 kb), only barriers and staging; krel < 31: diagonal,
+    // masked element-wise; later tiles see all 32 keys
+    const int krel = CAUSAL ? kKT * t - k0u : 0;
+    if (CAUSAL && krel < -63) continue;
 
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
@@ -709,6 +785,12 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_kv_kernel(AttnArgs a) {
           for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
             for (int r = 0; r < 4; ++r) s[qt][kt][r] = vk[kt] ? s[qt][kt][r] : -INFINITY;
+      }
+      if (CAUSAL && krel < 31) {   // hidden (query, key) pairs: P = 0
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+          for (int kt = 0; kt < 2; ++kt) causal_scores_q(s[qt][kt], krel + 32 * half + 16 * qt + 4 * g - 16 * kt - li);
       }
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt) {
@@ -829,32 +911,57 @@ AttnArgs make_args(int T, int H, float p, uint32_t seed, const uint32_t* seed_de
   return a;
 }
 
+template <bool CAUSAL>
+void launch_fwd(const AttnArgs& a, dim3 grid, hipStream_t stream) {
+  if (a.key_bits) {
+    if (a.thr) hipLaunchKernelGGL((attn_fwd_kernel<true, true, CAUSAL>), grid, dim3(64 * kAW), 0, stream, a);
+    else hipLaunchKernelGGL((attn_fwd_kernel<false, true, CAUSAL>), grid, dim3(64 * kAW), 0, stream, a);
+  } else if (a.thr) hipLaunchKernelGGL((attn_fwd_kernel<true, false, CAUSAL>), grid, dim3(64 * kAW), 0, stream, a);
+  else hipLaunchKernelGGL((attn_fwd_kernel<false, false, CAUSAL>), grid, dim3(64 * kAW), 0, stream, a);
+}
+
+template <bool CAUSAL>
+void launch_bwd(const AttnArgs& a, dim3 grid, hipStream_t stream) {
+  if (a.key_bits) {
+    if (a.thr) {
+      hipLaunchKernelGGL((attn_bwd_dq_kernel<true, true, CAUSAL>), grid, dim3(64 * kAW), 0, stream, a);
+      hipLaunchKernelGGL((attn_bwd_kv_kernel<true, true, CAUSAL>), grid, dim3(64 * kAW), 0, stream, a);
+    } else {
+      hipLaunchKernelGGL((attn_bwd_dq_kernel<false, true, CAUSAL>), grid, dim3(64 * kAW), 0, stream, a);
+      hipLaunchKernelGGL((attn_bwd_kv_kernel<false, true, CAUSAL>), grid, dim3(64 * kAW), 0, stream, a);
+    }
+  } else if (a.thr) {
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<true, false, CAUSAL>), grid, dim3(64 * kAW), 0, stream, a);
+    hipLaunchKernelGGL((attn_bwd_kv_kernel<true, false, CAUSAL>), grid, dim3(64 * kAW), 0, stream, a);
+  } else {
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<false, false, CAUSAL>), grid, dim3(64 * kAW), 0, stream, a);
+    hipLaunchKernelGGL((attn_bwd_kv_kernel<false, false, CAUSAL>), grid, dim3(64 * kAW), 0, stream, a);
+  }
+}
+
 }  // namespace
 
 bool attn_supported(int T, int D) { return D == kHD && T >= kRows && T % kRows == 0; }
 
 void attn_fwd(const void* qkv, void* out, float* lse, int B, int T, int H, float p, uint32_t seed,
-              const uint32_t* seed_dev, const uint32_t* key_bits, void* out_lo, hipStream_t stream) {
+              const uint32_t* seed_dev, const uint32_t* key_bits, void* out_lo, bool causal, hipStream_t stream) {
   AttnArgs a = make_args(T, H, p, seed, seed_dev);
-  a.out_lo = key_bits ? static_cast<uint16_t*>(out_lo) : nullptr;
+  a.out_lo = (key_bits || causal) ? static_cast<uint16_t*>(out_lo) : nullptr;
   a.qkv = static_cast<const uint16_t*>(qkv);
   a.o = static_cast<uint16_t*>(out);
   a.lse = lse;
   a.key_bits = key_bits;
   const dim3 grid((unsigned)(B * H * (T / kRows)));
-  if (key_bits) {
-    if (a.thr) hipLaunchKernelGGL((attn_fwd_kernel<true, true>), grid, dim3(64 * kAW), 0, stream, a);
-    else hipLaunchKernelGGL((attn_fwd_kernel<false, true>), grid, dim3(64 * kAW), 0, stream, a);
-  } else if (a.thr) hipLaunchKernelGGL((attn_fwd_kernel<true, false>), grid, dim3(64 * kAW), 0, stream, a);
-  else hipLaunchKernelGGL((attn_fwd_kernel<false, false>), grid, dim3(64 * kAW), 0, stream, a);
+  if (causal) launch_fwd<true>(a, grid, stream);
+  else launch_fwd<false>(a, grid, stream);
 }
 
 void attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int B,
               int T, int H, float p, uint32_t seed, const uint32_t* seed_dev, const uint32_t* key_bits,
-              const void* out_lo, hipStream_t stream) {
+              const void* out_lo, bool causal, hipStream_t stream) {
   AttnArgs a = make_args(T, H, p, seed, seed_dev);
   a.key_bits = key_bits;
-  a.out_lo = key_bits ? static_cast<uint16_t*>(const_cast<void*>(out_lo)) : nullptr;
+  a.out_lo = (key_bits || causal) ? static_cast<uint16_t*>(const_cast<void*>(out_lo)) : nullptr;
   a.qkv = static_cast<const uint16_t*>(qkv);
   a.out = static_cast<const uint16_t*>(out);
   a.dout = static_cast<const uint16_t*>(dout);
@@ -862,21 +969,8 @@ void attn_bwd(const void* qkv, const void* out, const void* dout, const float* l
   a.delta = delta;
   a.dqkv = static_cast<uint16_t*>(dqkv);
   const dim3 grid((unsigned)(B * H * (T / kRows)));
-  if (key_bits) {
-    if (a.thr) {
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<true, true>), grid, dim3(64 * kAW), 0, stream, a);
-      hipLaunchKernelGGL((attn_bwd_kv_kernel<true, true>), grid, dim3(64 * kAW), 0, stream, a);
-    } else {
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<false, true>), grid, dim3(64 * kAW), 0, stream, a);
-      hipLaunchKernelGGL((attn_bwd_kv_kernel<false, true>), grid, dim3(64 * kAW), 0, stream, a);
-    }
-  } else if (a.thr) {
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<true, false>), grid, dim3(64 * kAW), 0, stream, a);
-    hipLaunchKernelGGL((attn_bwd_kv_kernel<true, false>), grid, dim3(64 * kAW), 0, stream, a);
-  } else {
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<false, false>), grid, dim3(64 * kAW), 0, stream, a);
-    hipLaunchKernelGGL((attn_bwd_kv_kernel<false, false>), grid, dim3(64 * kAW), 0, stream, a);
-  }
+  if (causal) launch_bwd<true>(a, grid, stream);
+  else launch_bwd<false>(a, grid, stream);
 }
 
 void attn_pack_key_mask(const void* mask, int elem_size, bool is_float, uint32_t* bits, int B, int T,

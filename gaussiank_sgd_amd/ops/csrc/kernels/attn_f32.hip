@@ -37,6 +37,13 @@
 // -inf; the forward and the dQ kernel skip the arithmetic of key tiles without
 // a valid key and stop at the last tile that has one; the dK/dV kernel writes
 // zeros and returns for 128 masked keys.  MASK = false is the code without it.
+//
+// Causal mask (CAUSAL instantiations), as attn.hip: the forward and the dQ
+// kernel stop at tile 2 qb + 2 and mask the wave's diagonal tile element-wise,
+// waves 0 and 1 skip the arithmetic of the last tile; the dK/dV kernel starts
+// at query tile 2 kb (an even tile, so the two stages keep their parity); the
+// forward's lazy running max is kept per row.  CAUSAL = false is the code
+// without it.
 #include "common.h"
 #include "gk_kernels.h"
 #include "mfma_util.h"
@@ -125,7 +132,7 @@ __device__ __forceinline__ float ld1(const char* lds, uint32_t off) { return *re
 // ---------------------------------------------------------------------------
 // forward: 4 waves x 32 queries of one (batch, head); K / V tiles of 64 keys
 // ---------------------------------------------------------------------------
-template <bool DROP, bool MASK>
+template <bool DROP, bool MASK, bool CAUSAL = false>
 __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Args a) {
   extern __shared__ __attribute__((aligned(1024))) char smem[];   // 2 stages x (K, V)
   const uint32_t seed = DROP ? eff_seed(a) : 0u;
@@ -133,8 +140,15 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Arg
   const int li = lane & 15, g = lane >> 4;
   const int T = a.T, H = a.H;
   const int nqb = T / kRows;
-  const int blk = xcd_block();
-  const int bh = blk / nqb, qb = blk - bh * nqb;
+  int bh, qb;
+  if constexpr (CAUSAL) {   // heaviest row blocks first (attn_mask.h)
+    causal_block(nqb, bh, qb);
+    qb = nqb - 1 - qb;
+  } else {
+    const int blk = xcd_block();
+    bh = blk / nqb;
+    qb = blk - bh * nqb;
+  }
   const int b = bh / H, h = bh - b * H;
   const int64_t ld = 3LL * H * kHD;
   const float* base = a.qkv + (int64_t)b * T * ld;
@@ -149,7 +163,9 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Arg
   dk.issue(0, lds, wave);
   dv.issue(0, lds + kFTile, wave);
   // MASK: stop after the last tile with a valid key (0 tiles: an empty sequence)
-  const int nt = MASK ? mask_tiles(kbits, T >> 5, lane) : T / kKT;
+  const int ntm = MASK ? mask_tiles(kbits, T >> 5, lane) : T / kKT;
+  // CAUSAL: and after the workgroup's last visible tile, the one of its query 128 qb + 127
+  const int nt = CAUSAL ? min(ntm, 2 * qb + 2) : ntm;
   f32x4 qf[2][4];
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt)
@@ -169,6 +185,10 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Arg
   for (int qt = 0; qt < 2; ++qt) hrow[qt] = ((uint32_t)bh * T + q0 + 16 * qt + li) * (uint32_t)(T >> 1) + 2 * g;
 
   bool started = false;   // MASK: a tile with a valid key has been seen
+  // CAUSAL && MASK: the row has had no finite score yet.  Left padding or a hole over keys 0 .. q leaves a
+  // row's first tiles all -inf; such a row does not move m and takes the first-tile step at its first
+  // finite score (a row that never has one ends with l = 0: out = 0, lse = 0)
+  bool fresh[2] = {true, true};
   for (int t = 0; t < nt; ++t) {
     uint32_t w0 = ~0u, w1 = ~0u;   // valid bits of the tile's 64 keys (workgroup-uniform)
     if (MASK) {
@@ -185,7 +205,11 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Arg
       dk.issue((t + 1) * tstep, nx, wave);
       dv.issue((t + 1) * tstep, nx + kFTile, wave);
     }
-    if (MASK && (w0 | w1) == 0u) continue;   // no valid key: staged and waited for, no arithmetic
+    // CAUSAL, per wave (wave-uniform): the tile is fully visible (qrel >= 63), diagonal, or past the wave's
+    // last query (qrel < -31: waves 0 and 1 on the workgroup's last tile)
+    const int qrel = CAUSAL ? q0 - kKT * t : 0;
+    // no valid / no visible key: staged and waited for, no arithmetic
+    if ((MASK && (w0 | w1) == 0u) || (CAUSAL && qrel < -31)) continue;
 
     // S^T - m (log2 units)
     f32x4 s[2][4];
@@ -195,6 +219,7 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Arg
       for (int kt = 0; kt < 4; ++kt) s[qt][kt] = splat4(-m[qt]);
     // masked keys: -inf in the initial accumulator, which the MFMAs carry through
     if (MASK && (w0 & w1) != ~0u) mask_scores_t(s, w0 >> (4 * g), w1 >> (4 * g));
+    if (CAUSAL && qrel < 63) causal_scores_t(s, qrel + li - 4 * g);
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
@@ -203,7 +228,8 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Arg
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt) s[qt][kt] = mfma16(kv, qf[qt][c], s[qt][kt]);
       }
-    // the first tile (MASK: the first with a valid key, where every row has a finite max)
+    // the first tile (MASK: the first with a valid key, where every row has a finite max; CAUSAL alone:
+    // tile 0, key 0 is visible to every query; CAUSAL && MASK: per row, fresh[])
     const bool first = MASK ? !started : t == 0;
     started = true;
 
@@ -213,10 +239,20 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Arg
 #pragma unroll
       for (int kt = 1; kt < 4; ++kt)
         mx = fmaxf(mx, fmaxf(fmaxf(s[qt][kt][0], s[qt][kt][1]), fmaxf(s[qt][kt][2], s[qt][kt][3])));
-      if (first || __ballot(mx > kLazy) != 0) {
+      if ((CAUSAL && MASK) ? __ballot(fresh[qt] || mx > kLazy) != 0 : first || __ballot(mx > kLazy) != 0) {
         mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float d = first ? mx : fmaxf(mx, 0.f);
+        float d;
+        if constexpr (CAUSAL) {
+          // per row: a row below the threshold keeps its m bit for bit (d = 0 changes nothing), so what
+          // another row of the wave scores -- a later query sees keys this one does not -- cannot reach it
+          const bool fr = MASK ? fresh[qt] : first;
+          const bool dark = MASK && mx == -INFINITY;   // no finite score in this tile
+          d = fr ? (dark ? 0.f : mx) : (mx > kLazy ? mx : 0.f);
+          if (MASK) fresh[qt] = fr && dark;
+        } else {
+          d = first ? mx : fmaxf(mx, 0.f);
+        }
         m[qt] += d;
         const float al = fexp2(-d);
         l[qt] *= al;
@@ -284,7 +320,7 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Arg
 // backward, dQ (+ delta = rowsum(dO * O)): per key tile S^T = c K Q^T - lse,
 // dZ^T = V dO^T - delta', dS^T = P^T (dP^T - delta), dQ^T += K^T dS^T
 // ---------------------------------------------------------------------------
-template <bool DROP, bool MASK>
+template <bool DROP, bool MASK, bool CAUSAL = false>
 __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_dq_kernel(AttnF32Args a) {
   extern __shared__ __attribute__((aligned(1024))) char smem[];   // 2 stages x (K, V)
   const uint32_t seed = DROP ? eff_seed(a) : 0u;
@@ -292,8 +328,15 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_dq_kernel(AttnF32
   const int li = lane & 15, g = lane >> 4;
   const int T = a.T, H = a.H;
   const int nqb = T / kRows;
-  const int blk = xcd_block();
-  const int bh = blk / nqb, qb = blk - bh * nqb;
+  int bh, qb;
+  if constexpr (CAUSAL) {   // heaviest row blocks first (attn_mask.h)
+    causal_block(nqb, bh, qb);
+    qb = nqb - 1 - qb;
+  } else {
+    const int blk = xcd_block();
+    bh = blk / nqb;
+    qb = blk - bh * nqb;
+  }
   const int b = bh / H, h = bh - b * H;
   const int64_t ld = 3LL * H * kHD, ldo = (int64_t)H * kHD;
   const float* base = a.qkv + (int64_t)b * T * ld;
@@ -308,7 +351,9 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_dq_kernel(AttnF32
   dk.issue(0, lds, wave);
   dv.issue(0, lds + kFTile, wave);
   // MASK: stop after the last tile with a valid key (0 tiles: an empty sequence)
-  const int nt = MASK ? mask_tiles(kbits, T >> 5, lane) : T / kKT;
+  const int ntm = MASK ? mask_tiles(kbits, T >> 5, lane) : T / kKT;
+  // CAUSAL: and after the workgroup's last visible tile, the one of its query 128 qb + 127
+  const int nt = CAUSAL ? min(ntm, 2 * qb + 2) : ntm;
   f32x4 qf[2][4], df[2][4];
   float nlse[2], del[2], ndel[2];
   uint32_t hrow[2];
@@ -356,7 +401,9 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_dq_kernel(AttnF32
       dk.issue((t + 1) * tstep, nx, wave);
       dv.issue((t + 1) * tstep, nx + kFTile, wave);
     }
-    if (MASK && (w0 | w1) == 0u) continue;   // no valid key: P = 0 for the whole tile
+    const int qrel = CAUSAL ? q0 - kKT * t : 0;   // as in the forward
+    // no valid / no visible key: P = 0 for the whole tile
+    if ((MASK && (w0 | w1) == 0u) || (CAUSAL && qrel < -31)) continue;
 
     f32x4 s[2][4], dz[2][4];
 #pragma unroll
@@ -368,6 +415,7 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_dq_kernel(AttnF32
       }
     // masked keys: -inf through the MFMAs, so P = exp2(-inf) and with it dS are exactly 0
     if (MASK && (w0 & w1) != ~0u) mask_scores_t(s, w0 >> (4 * g), w1 >> (4 * g));
+    if (CAUSAL && qrel < 63) causal_scores_t(s, qrel + li - 4 * g);
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt) {
 #pragma unroll
@@ -439,7 +487,7 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_dq_kernel(AttnF32
 // ---------------------------------------------------------------------------
 constexpr int kKvStage = 2 * kFTile + 512;   // Q tile, dO tile, lse[64], delta[64]
 
-template <bool DROP, bool MASK>
+template <bool DROP, bool MASK, bool CAUSAL = false>
 __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_kv_kernel(AttnF32Args a) {
   extern __shared__ __attribute__((aligned(1024))) char smem[];   // 2 x kKvStage
   const uint32_t seed = DROP ? eff_seed(a) : 0u;
@@ -447,8 +495,14 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_kv_kernel(AttnF32
   const int li = lane & 15, g = lane >> 4;
   const int T = a.T, H = a.H;
   const int nkb = T / kRows;
-  const int blk = xcd_block();
-  const int bh = blk / nkb, kb = blk - bh * nkb;
+  int bh, kb;
+  if constexpr (CAUSAL) {   // heaviest key blocks (the first ones) first (attn_mask.h)
+    causal_block(nkb, bh, kb);
+  } else {
+    const int blk = xcd_block();
+    bh = blk / nkb;
+    kb = blk - bh * nkb;
+  }
   const int b = bh / H, h = bh - b * H;
   const int64_t ld = 3LL * H * kHD, ldo = (int64_t)H * kHD;
   const float* base = a.qkv + (int64_t)b * T * ld;
@@ -486,8 +540,10 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_kv_kernel(AttnF32
       __builtin_amdgcn_global_load_lds((wave ? delp : lsep) + t * kKT + lane, dst + 2 * kFTile + wave * 256, 4, 0, 0);
   };
   const int nt = T / kKT;
+  // CAUSAL: the first query tile that sees any of the workgroup's keys (even, so the stages keep t & 1)
+  const int t0 = CAUSAL ? 2 * kb : 0;
 
-  stage(0, 0);
+  stage(t0, 0);
   f32x4 kf[2][4], vf[2][4];
 #pragma unroll
   for (int kt = 0; kt < 2; ++kt)
@@ -506,7 +562,7 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_kv_kernel(AttnF32
   const uint32_t hbase = (uint32_t)bh * T * (uint32_t)(T >> 1);
   const uint32_t hsh = 16u * (uint32_t)(li & 1);
 
-  for (int t = 0; t < nt; ++t) {
+  for (int t = t0; t < nt; ++t) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
@@ -515,6 +571,11 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_kv_kernel(AttnF32
     const float* Ls = reinterpret_cast<const float*>(Qs + 2 * kFTile);
     if (t + 1 < nt) stage(t + 1, (t + 1) & 1);
     if (MASK && ww == 0u) continue;   // no valid key in this wave: dK = dV = 0, only barriers and staging
+    // CAUSAL, per wave: krel = (tile's first query) - (wave's first key).  krel < -63: no query of the tile
+    // sees a key of the wave (waves 2 and 3 on tile 2 kb), only barriers and staging; krel < 31: diagonal,
+    // masked element-wise; later tiles see all 32 keys
+    const int krel = CAUSAL ? kKT * t - k0 : 0;
+    if (CAUSAL && krel < -63) continue;
 
 #pragma unroll 1
     for (int qt = 0; qt < 4; ++qt) {   // not unrolled: one 16-query tile's operands live at a time
@@ -543,6 +604,10 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_kv_kernel(AttnF32
         for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
           for (int r = 0; r < 4; ++r) s[kt][r] = vk[kt] ? s[kt][r] : -INFINITY;
+      }
+      if (CAUSAL && krel < 31) {   // hidden (query, key) pairs: P = 0
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt) causal_scores_q(s[kt], krel + qr - 16 * kt - li);
       }
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt) {
@@ -614,28 +679,53 @@ void launch(K kern, int nblocks, int lds, const AttnF32Args& a, hipStream_t stre
   hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(64 * kWaves), lds, stream, a);
 }
 
+template <bool CAUSAL>
+void launch_fwd(int nb, const AttnF32Args& a, hipStream_t stream) {
+  if (a.key_bits) {
+    if (a.thr) launch(attn_f32_fwd_kernel<true, true, CAUSAL>, nb, 4 * kFTile, a, stream);
+    else launch(attn_f32_fwd_kernel<false, true, CAUSAL>, nb, 4 * kFTile, a, stream);
+  } else if (a.thr) launch(attn_f32_fwd_kernel<true, false, CAUSAL>, nb, 4 * kFTile, a, stream);
+  else launch(attn_f32_fwd_kernel<false, false, CAUSAL>, nb, 4 * kFTile, a, stream);
+}
+
+template <bool CAUSAL>
+void launch_bwd(int nb, const AttnF32Args& a, hipStream_t stream) {
+  if (a.key_bits) {
+    if (a.thr) {
+      launch(attn_f32_bwd_dq_kernel<true, true, CAUSAL>, nb, 4 * kFTile, a, stream);
+      launch(attn_f32_bwd_kv_kernel<true, true, CAUSAL>, nb, 2 * kKvStage, a, stream);
+    } else {
+      launch(attn_f32_bwd_dq_kernel<false, true, CAUSAL>, nb, 4 * kFTile, a, stream);
+      launch(attn_f32_bwd_kv_kernel<false, true, CAUSAL>, nb, 2 * kKvStage, a, stream);
+    }
+  } else if (a.thr) {
+    launch(attn_f32_bwd_dq_kernel<true, false, CAUSAL>, nb, 4 * kFTile, a, stream);
+    launch(attn_f32_bwd_kv_kernel<true, false, CAUSAL>, nb, 2 * kKvStage, a, stream);
+  } else {
+    launch(attn_f32_bwd_dq_kernel<false, false, CAUSAL>, nb, 4 * kFTile, a, stream);
+    launch(attn_f32_bwd_kv_kernel<false, false, CAUSAL>, nb, 2 * kKvStage, a, stream);
+  }
+}
+
 }  // namespace
 
 bool attn_f32_supported(int T, int D) { return D == kHD && T >= kRows && T % kRows == 0; }
 
 void attn_f32_fwd(const float* qkv, float* out, float* lse, int B, int T, int H, float p, uint32_t seed,
-                  const uint32_t* seed_dev, const uint32_t* key_bits, hipStream_t stream) {
+                  const uint32_t* seed_dev, const uint32_t* key_bits, bool causal, hipStream_t stream) {
   AttnF32Args a = make_args(T, H, p, seed, seed_dev);
   a.qkv = qkv;
   a.o = out;
   a.lse = lse;
   a.key_bits = key_bits;
   const int nb = B * H * (T / kRows);
-  if (key_bits) {
-    if (a.thr) launch(attn_f32_fwd_kernel<true, true>, nb, 4 * kFTile, a, stream);
-    else launch(attn_f32_fwd_kernel<false, true>, nb, 4 * kFTile, a, stream);
-  } else if (a.thr) launch(attn_f32_fwd_kernel<true, false>, nb, 4 * kFTile, a, stream);
-  else launch(attn_f32_fwd_kernel<false, false>, nb, 4 * kFTile, a, stream);
+  if (causal) launch_fwd<true>(nb, a, stream);
+  else launch_fwd<false>(nb, a, stream);
 }
 
 void attn_f32_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* delta, float* dqkv,
                   int B, int T, int H, float p, uint32_t seed, const uint32_t* seed_dev, const uint32_t* key_bits,
-                  hipStream_t stream) {
+                  bool causal, hipStream_t stream) {
   AttnF32Args a = make_args(T, H, p, seed, seed_dev);
   a.qkv = qkv;
   a.out = out;
@@ -645,21 +735,8 @@ void attn_f32_bwd(const float* qkv, const float* out, const float* dout, const f
   a.dqkv = dqkv;
   a.key_bits = key_bits;
   const int nb = B * H * (T / kRows);
-  if (key_bits) {
-    if (a.thr) {
-      launch(attn_f32_bwd_dq_kernel<true, true>, nb, 4 * kFTile, a, stream);
-      launch(attn_f32_bwd_kv_kernel<true, true>, nb, 2 * kKvStage, a, stream);
-    } else {
-      launch(attn_f32_bwd_dq_kernel<false, true>, nb, 4 * kFTile, a, stream);
-      launch(attn_f32_bwd_kv_kernel<false, true>, nb, 2 * kKvStage, a, stream);
-    }
-  } else if (a.thr) {
-    launch(attn_f32_bwd_dq_kernel<true, false>, nb, 4 * kFTile, a, stream);
-    launch(attn_f32_bwd_kv_kernel<true, false>, nb, 2 * kKvStage, a, stream);
-  } else {
-    launch(attn_f32_bwd_dq_kernel<false, false>, nb, 4 * kFTile, a, stream);
-    launch(attn_f32_bwd_kv_kernel<false, false>, nb, 2 * kKvStage, a, stream);
-  }
+  if (causal) launch_bwd<true>(nb, a, stream);
+  else launch_bwd<false>(nb, a, stream);
 }
 
 }  // namespace gk

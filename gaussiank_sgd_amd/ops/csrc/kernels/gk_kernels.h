@@ -575,22 +575,25 @@ void wgrad3_acc(const void* dy, const void* x, const void* zero, int N, int H, i
 // a [B, T] mask of 1-, 2-, 4- or 8-byte elements, nonzero = valid).  Masked
 // keys get probability 0 and zero dK / dV; lse runs over the valid keys; a
 // sequence without a valid key gives out = 0, lse = 0 and zero gradients.
+// causal: query q sees key k iff k <= q (AND the key's bit, with key_bits); a
+// query without a visible valid key gives out = 0, lse = 0, zero dQ and adds
+// nothing to dK / dV.  Key tiles past a workgroup's last query are not visited.
 // ---------------------------------------------------------------------------
 bool attn_supported(int T, int D);
 // fp32 variants (attn_f32.hip): same layouts, fp32 qkv / out / dout / dqkv
 bool attn_f32_supported(int T, int D);
 void attn_f32_fwd(const float* qkv, float* out, float* lse, int B, int T, int H, float p, uint32_t seed,
-                  const uint32_t* seed_dev, const uint32_t* key_bits, hipStream_t stream);
+                  const uint32_t* seed_dev, const uint32_t* key_bits, bool causal, hipStream_t stream);
 void attn_f32_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* delta, float* dqkv,
                   int B, int T, int H, float p, uint32_t seed, const uint32_t* seed_dev, const uint32_t* key_bits,
-                  hipStream_t stream);
-// out_lo (optional, bf16 kernels with key_bits only): bf16 [B, T, H, 64], the part of the output that its
+                  bool causal, hipStream_t stream);
+// out_lo (optional, bf16 kernels with key_bits or causal only): bf16 [B, T, H, 64], the part of the output that its
 // bf16 rounding dropped; the forward writes it and the backward adds it back for delta = rowsum(dO * O)
 void attn_fwd(const void* qkv, void* out, float* lse, int B, int T, int H, float p, uint32_t seed,
-              const uint32_t* seed_dev, const uint32_t* key_bits, void* out_lo, hipStream_t stream);
+              const uint32_t* seed_dev, const uint32_t* key_bits, void* out_lo, bool causal, hipStream_t stream);
 void attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int B,
               int T, int H, float p, uint32_t seed, const uint32_t* seed_dev, const uint32_t* key_bits,
-              const void* out_lo, hipStream_t stream);
+              const void* out_lo, bool causal, hipStream_t stream);
 void attn_pack_key_mask(const void* mask, int elem_size, bool is_float, uint32_t* bits, int B, int T,
                         hipStream_t stream);
 void attn_dropout_mask(uint8_t* mask, int B, int H, int T, float p, uint32_t seed, const uint32_t* seed_dev,

@@ -12,7 +12,7 @@ Same command line as the reference:
   ``DLTrainer.test`` scores it on the WHOLE test split of ``--data-dir``
   (synthetic batches when the directory holds no data);
 * the best accuracy (lowest perplexity / WER for lstm / lstman4, and
-  perplexity for BERT) is logged after every epoch, and everything goes to
+  perplexity for BERT and GPT) is logged after every epoch, and everything goes to
   ``<model-path>/evaluate.log`` as well (reference :68-71).
 
 Checkpoints are read with ``weights_only=True``; a missing epoch file is
@@ -62,7 +62,7 @@ def evaluate(model_path, dnn, dataset, data_dir="./data", nepochs=90, batch_size
     device = device or ("cuda" if torch.cuda.is_available() else "cpu")
     trainer = DLTrainer(0, 1, dist=False, ngpus=1, batch_size=batch_size, is_weak_scaling=True, dataset=dataset,
                         dnn=dnn, data_dir=data_dir, lr=lr, nworkers=1, device=device)
-    lower_is_better = dnn in ("lstm", "lstman4") or dnn.startswith("bert")
+    lower_is_better = dnn in ("lstm", "lstman4") or dnn.startswith(("bert", "gpt"))
     best, best_epoch = None, -1
     results = {}
     for i in range(1, nepochs + 1):

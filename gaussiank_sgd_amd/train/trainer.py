@@ -29,17 +29,17 @@ import torch.nn as nn
 
 from .. import settings
 from ..data import DATASETS, SyntheticData
-from ..models import MaskedLMLoss, create_net, repackage_hidden
+from ..models import CausalLMLoss, MaskedLMLoss, create_net, repackage_hidden
 from ..ops import xent
 from ..optim import LAMB, sgd_param_groups
 from ..settings import logger
 from ..utils import trace
 from . import schedules
 
-_support_datasets = ["imagenet", "cifar10", "an4", "ptb", "mnist", "mnist32", "wikipedia"]
+_support_datasets = ["imagenet", "cifar10", "an4", "ptb", "mnist", "mnist32", "wikipedia", "openwebtext"]
 _support_dnns = ["resnet50", "googlenet", "inceptionv4", "inceptionv3", "vgg16i", "alexnet", "resnet20", "resnet56",
                  "resnet110", "vgg19", "vgg16", "lstman4", "lstm", "mnistnet", "fcn5net", "lenet", "lr", "bert",
-                 "bert_tiny", "resnet18", "resnet34", "resnet101", "resnet152", "densenet100", "resnext29"]
+                 "bert_tiny", "gpt2", "gpt_tiny", "resnet18", "resnet34", "resnet101", "resnet152", "densenet100", "resnext29"]
 
 
 # AN4 character set (the reference's labels.json): index 0 is the CTC blank
@@ -164,6 +164,8 @@ class DLTrainer:
         self.average_iter = 0
         if self.dnn.startswith("bert"):
             self.criterion = MaskedLMLoss()
+        elif self.dnn.startswith("gpt"):
+            self.criterion = CausalLMLoss()
         elif self.dnn == "lstman4":
             self.criterion = nn.CTCLoss(blank=0, reduction="sum", zero_infinity=True)
         else:
@@ -232,9 +234,14 @@ class DLTrainer:
             ds = "mnist32"
         if self.dnn.startswith("bert"):
             ds = "wikipedia"
+        if self.dnn.startswith("gpt"):
+            ds = "openwebtext"
         if ds not in DATASETS:
             raise ValueError("Unsupport dataset: %s" % ds)
         vocab = None
+        if self.dnn == "gpt_tiny":
+            vocab = 1024
+            seq_len = seq_len or 128
         if self.dnn == "bert_tiny":
             vocab = 1024
             seq_len = seq_len or 128
@@ -371,6 +378,9 @@ class DLTrainer:
                 else:                                     # dense [B, T] labels, -100 = unmasked
                     outputs = self.net(inputs)
                     loss = self.criterion(outputs, labels)
+            elif self.dnn.startswith("gpt"):
+                outputs = self.net(inputs)
+                loss = self.criterion(outputs, labels)     # [B, T] next-token labels
             elif self.dnn == "lstman4":
                 targets, tgt_lens, in_lens = labels
                 outputs, out_lens = self.net(inputs, in_lens)
@@ -438,7 +448,7 @@ class DLTrainer:
             ld = loss.detach()
             loss_sum = ld if loss_sum is None else loss_sum + ld
             self._epoch_loss_acc = ld.clone() if self._epoch_loss_acc is None else self._epoch_loss_acc + ld
-            if self.dnn not in ("lstm", "lstman4") and not self.dnn.startswith("bert"):
+            if self.dnn not in ("lstm", "lstman4") and not self.dnn.startswith(("bert", "gpt")):
                 acc1, = self.cal_accuracy(outputs.detach(), labels, topk=(1,))
                 self._acc_acc = acc1 if self._acc_acc is None else self._acc_acc + acc1
                 self._acc_n += 1
@@ -505,7 +515,7 @@ class DLTrainer:
                 if self.dnn == "lstm":
                     costs += float(loss) * self.num_steps
                     steps += self.num_steps
-                elif not self.dnn.startswith("bert"):
+                elif not self.dnn.startswith(("bert", "gpt")):
                     k5 = min(5, outputs.shape[1])
                     a1, a5 = self.cal_accuracy(outputs.float(), labels, topk=(1, k5))
                     top1.append(float(a1))
@@ -515,7 +525,7 @@ class DLTrainer:
             acc, acc5 = float(np.exp(costs / max(1, steps))), 0.0
         elif self.dnn == "lstman4":
             acc, acc5 = wer_sum / max(1, utterances), 0.0
-        elif self.dnn.startswith("bert"):
+        elif self.dnn.startswith(("bert", "gpt")):   # perplexity
             acc, acc5 = float(np.exp(test_loss)), 0.0
         else:
             acc, acc5 = float(np.mean(top1)), float(np.mean(top5))
