@@ -473,7 +473,10 @@ class BNAct(nn.BatchNorm2d):
         the fused training path."""
         relu = self.act == "relu"
         pool = self.pool
-        if self.training and self.fused and self.track_running_stats and fused_bn_available(x) and \
+        # one value per channel (M = 1) or none: nn.BatchNorm2d raises in training at M = 1, where the fused
+        # finalize would go on silently (and divide by M = 0), so the PyTorch path below answers
+        if self.training and self.fused and self.track_running_stats and x.numel() // max(x.shape[1], 1) > 1 and \
+                fused_bn_available(x) and \
                 (pool is None or (residual is None and x.numel() // x.shape[1] < 2 ** 32)):
             nbt = self.num_batches_tracked
             if self.momentum is None:
@@ -518,7 +521,8 @@ class BNAct(nn.BatchNorm2d):
 
     def fused_ok(self, x: torch.Tensor) -> bool:
         """Will ``forward(x)`` take the fused training path?"""
-        return bool(self.training and self.fused and self.track_running_stats and fused_bn_available(x))
+        return bool(self.training and self.fused and self.track_running_stats and
+                    x.numel() // max(x.shape[1], 1) > 1 and fused_bn_available(x))
 
     def deferred(self, x: torch.Tensor, stats=None) -> Optional[torch.Tensor]:
         """BN of ``x`` with the apply pass deferred into the consumer (see

@@ -18,6 +18,15 @@
 // thread owns 16 contiguous bytes of channels (8 bf16 / 4 fp32) and walks
 // rows, so every wave reads whole 1-KiB contiguous runs.  Statistics are
 // accumulated in fp32 per thread and combined in fp64.
+// Accuracy envelope: the variance is one-pass (q / M - mean^2) from fp32
+// partials, so its error grows with (mean / std)^2 -- measured on MI355X
+// (fp32, M = 6272, C = 64, 64 workgroups; tests/bn_cases.py family N,
+// profiles/bn_kernels_tolerances.txt), max |y - fp64|: 5.9e-7 at mean / std
+// 0 / 1, 1.2e-6 at 4 / 1, 1.6e-5 at 16 / 1 and 5.7e-2 at 100 / 0.1 (fp32
+// PyTorch on the CPU: 6.7e-7, 1.5e-6, 4.3e-6, 2.1e-4).
+// Two or three values per channel (M = 2, 3) hit the same loss wherever a
+// channel's sample mean is large against its sample deviation: dx there was
+// up to 390x the error of nn.BatchNorm2d (2.9e-2 against 7.5e-5).
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -198,17 +207,19 @@ __global__ __launch_bounds__(kBlock) void bn_stats_kernel(const T* __restrict__ 
     sh[1][threadIdx.x * V + i] = q[i];
   }
   __syncthreads();
-  // reduce over row lanes: thread t < ct handles channel (tile-local) t
+  // reduce over row lanes: thread t < ct handles channel (tile-local) t.  The rl lane sums are added in
+  // fp64 (up to 256 of them when C / V has no divisor <= 64 but 1: an fp32 chain that long cost y 3-4x the
+  // error of a plain fp32 batch norm, tests/bn_cases.py); the partial itself stays fp32.
   for (int cl = threadIdx.x; cl < g.ct; cl += kBlock) {
     const int t = cl / V, i = cl % V;
-    float a = 0.f, b = 0.f;
+    double a = 0.0, b = 0.0;
     for (int l = 0; l < g.rl; ++l) {
-      a += sh[0][(l * g.tpr + t) * V + i];
-      b += sh[1][(l * g.tpr + t) * V + i];
+      a += (double)sh[0][(l * g.tpr + t) * V + i];
+      b += (double)sh[1][(l * g.tpr + t) * V + i];
     }
     const int c = blockIdx.x * g.ct + cl;
-    psum[(int64_t)blockIdx.y * C + c] = a;
-    psq[(int64_t)blockIdx.y * C + c] = b;
+    psum[(int64_t)blockIdx.y * C + c] = (float)a;
+    psq[(int64_t)blockIdx.y * C + c] = (float)b;
   }
 }
 
@@ -712,16 +723,16 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_reduce_kernel(Src src, const T*
     sh[1][threadIdx.x * V + i] = sg[i];
   }
   __syncthreads();
-  for (int cl = threadIdx.x; cl < g.ct; cl += kBlock) {
+  for (int cl = threadIdx.x; cl < g.ct; cl += kBlock) {   // lane sums added in fp64, as in bn_stats_kernel
     const int t = cl / V, i = cl % V;
-    float a = 0.f, b = 0.f;
+    double a = 0.0, b = 0.0;
     for (int l = 0; l < g.rl; ++l) {
-      a += sh[0][(l * g.tpr + t) * V + i];
-      b += sh[1][(l * g.tpr + t) * V + i];
+      a += (double)sh[0][(l * g.tpr + t) * V + i];
+      b += (double)sh[1][(l * g.tpr + t) * V + i];
     }
     const int c = blockIdx.x * g.ct + cl;
-    pdb[(int64_t)blockIdx.y * C + c] = a;
-    pdg[(int64_t)blockIdx.y * C + c] = b;
+    pdb[(int64_t)blockIdx.y * C + c] = (float)a;
+    pdg[(int64_t)blockIdx.y * C + c] = (float)b;
   }
 }
 
@@ -1025,14 +1036,14 @@ __global__ __launch_bounds__(kBlock) void bn_pool_tile_kernel(const T* __restric
   __syncthreads();
   for (int cl = threadIdx.x; cl < g.ct; cl += kBlock) {
     const int tt = cl / V, i = cl % V;
-    float s0 = 0.f, s1 = 0.f;
+    double s0 = 0.0, s1 = 0.0;   // lane sums added in fp64, as in bn_stats_kernel
     for (int l = 0; l < g.rl; ++l) {
-      s0 += sh[0][(l * g.tpr + tt) * V + i];
-      s1 += sh[1][(l * g.tpr + tt) * V + i];
+      s0 += (double)sh[0][(l * g.tpr + tt) * V + i];
+      s1 += (double)sh[1][(l * g.tpr + tt) * V + i];
     }
     const int c = blockIdx.x * g.ct + cl;
-    pdb[(int64_t)blockIdx.y * C + c] = s0;
-    pdg[(int64_t)blockIdx.y * C + c] = s1;
+    pdb[(int64_t)blockIdx.y * C + c] = (float)s0;
+    pdg[(int64_t)blockIdx.y * C + c] = (float)s1;
   }
 }
 
@@ -1507,11 +1518,13 @@ template <typename T, bool TWIN>
 void bn_pool_backward_tw(const T* dy, const T* dy2, const uint8_t* amax, const T* x, T* dx, int64_t M, int C,
                          PoolGeo pg, const float* w, const float* mean, const float* invstd, float* dgamma,
                          float* dbeta, float* ws, float* gw_acc, float* gb_acc, hipStream_t s) {
-  if (pg.s == 2 && pg.k <= 4) {  // every window reaching tile th has oh in {th-1, th}
+  const int TH = (pg.H + pg.p + pg.s - 1) / pg.s, TW = (pg.W + pg.p + pg.s - 1) / pg.s;
+  const int64_t ntiles = M / ((int64_t)pg.H * pg.W) * TH * TW;
+  // every window reaching tile th has oh in {th-1, th}.  ntiles <= M: the workspace holds the partials of a
+  // grid over M rows (bn_workspace_floats); a 1-pixel-wide plane under a padded pool has more tiles than
+  // pixels and would get more row chunks than that, so it takes the per-pixel gather.
+  if (pg.s == 2 && pg.k <= 4 && ntiles <= M) {
     // tile-ordered fast path (3x3/s2 stem pool)
-    const int TH = (pg.H + pg.p + pg.s - 1) / pg.s, TW = (pg.W + pg.p + pg.s - 1) / pg.s;
-    const int64_t N = M / ((int64_t)pg.H * pg.W);
-    const int64_t ntiles = N * TH * TW;
     const Geo g = make_geo<T>(ntiles, C, kPoolTargetBlocks);
     float* pdb = ws;
     float* pdg = ws + (int64_t)g.gy * C;
