@@ -170,61 +170,45 @@ def reference_attention(qkv: torch.Tensor, heads: int, p: float = 0.0, seed: int
     return o.transpose(1, 2).reshape(B, T, heads * d)
 
 
-class _FlashAttnFn(torch.autograd.Function):
-    @staticmethod
+def _flash_attn_fn(name: str, dtype, fwd: str, bwd: str, keep_lo: bool):
+    """The autograd function over the native ops ``fwd`` / ``bwd`` for activations of ``dtype``.
+    ``keep_lo``: with a mask, rows with few valid keys have concentrated probabilities, where dP and
+    delta = rowsum(dO * O) nearly cancel, so the bf16 forward also keeps what the rounding of O dropped
+    (``out_lo``; causal: the first rows of a sequence are such rows) and both ops take it."""
+
     def forward(ctx, qkv, heads, p, seed, seed_dev=None, key_bits=None, causal=False):
         # seed_dev: the graph replay word (ops.graph_seed_word) under capture --
         # forward and backward of one replay read the same word
         # key_bits: the packed key mask (pack_key_mask), shared with the backward
         # causal: a Python bool, it picks the kernels' CAUSAL instantiations
         B, T, _ = qkv.shape
-        out = torch.empty(B, T, heads * HEAD_DIM, dtype=torch.bfloat16, device=qkv.device)
+        out = torch.empty(B, T, heads * HEAD_DIM, dtype=dtype, device=qkv.device)
         lse = torch.empty(B * heads * T, dtype=torch.float32, device=qkv.device)
-        # with a mask, rows with few valid keys have concentrated probabilities, where dP and delta =
-        # rowsum(dO * O) nearly cancel: the forward also keeps what the bf16 rounding of O dropped
-        # (causal: the first rows of a sequence are such rows)
-        out_lo = None if key_bits is None and not causal else torch.empty_like(out)
-        _ops().attn_fwd(qkv, out, lse, int(heads), float(p), int(seed), seed_dev, key_bits, out_lo, bool(causal))
-        ctx.save_for_backward(qkv, out, lse, key_bits, out_lo)
+        lo = (None if key_bits is None and not causal else torch.empty_like(out),) if keep_lo else ()
+        getattr(_ops(), fwd)(qkv, out, lse, int(heads), float(p), int(seed), seed_dev, key_bits, *lo,
+                             bool(causal))
+        ctx.save_for_backward(qkv, out, lse, key_bits, *lo)
         ctx.heads, ctx.p, ctx.seed, ctx.seed_dev = int(heads), float(p), int(seed), seed_dev
         ctx.causal = bool(causal)
         return out
 
-    @staticmethod
     def backward(ctx, dout):
-        qkv, out, lse, key_bits, out_lo = ctx.saved_tensors
-        dout = dout.to(torch.bfloat16).contiguous()
+        qkv, out, lse, key_bits, *lo = ctx.saved_tensors
+        dout = dout.to(dtype).contiguous()
         delta = torch.empty_like(lse)
         dqkv = torch.empty_like(qkv)
-        _ops().attn_bwd(qkv, out, dout, lse, delta, dqkv, ctx.heads, ctx.p, ctx.seed, ctx.seed_dev, key_bits, out_lo,
-                        ctx.causal)
+        getattr(_ops(), bwd)(qkv, out, dout, lse, delta, dqkv, ctx.heads, ctx.p, ctx.seed, ctx.seed_dev, key_bits,
+                             *lo, ctx.causal)
         return dqkv, None, None, None, None, None, None
 
+    # the class statement's own call, so that the class and its autograd node carry ``name``
+    return type(torch.autograd.Function)(name, (torch.autograd.Function,),
+                                         {"forward": staticmethod(forward), "backward": staticmethod(backward)})
 
-class _FlashAttnF32Fn(torch.autograd.Function):
-    """fp32 twin of _FlashAttnFn (csrc/kernels/attn_f32.hip): fp32 operands on
-    v_mfma_f32_16x16x4_f32, the same dropout hashes."""
 
-    @staticmethod
-    def forward(ctx, qkv, heads, p, seed, seed_dev=None, key_bits=None, causal=False):
-        B, T, _ = qkv.shape
-        out = torch.empty(B, T, heads * HEAD_DIM, dtype=torch.float32, device=qkv.device)
-        lse = torch.empty(B * heads * T, dtype=torch.float32, device=qkv.device)
-        _ops().attn_f32_fwd(qkv, out, lse, int(heads), float(p), int(seed), seed_dev, key_bits, bool(causal))
-        ctx.save_for_backward(qkv, out, lse, key_bits)
-        ctx.heads, ctx.p, ctx.seed, ctx.seed_dev = int(heads), float(p), int(seed), seed_dev
-        ctx.causal = bool(causal)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        qkv, out, lse, key_bits = ctx.saved_tensors
-        dout = dout.to(torch.float32).contiguous()
-        delta = torch.empty_like(lse)
-        dqkv = torch.empty_like(qkv)
-        _ops().attn_f32_bwd(qkv, out, dout, lse, delta, dqkv, ctx.heads, ctx.p, ctx.seed, ctx.seed_dev, key_bits,
-                            ctx.causal)
-        return dqkv, None, None, None, None, None, None
+_FlashAttnFn = _flash_attn_fn("_FlashAttnFn", torch.bfloat16, "attn_fwd", "attn_bwd", keep_lo=True)
+# the fp32 twin (csrc/kernels/attn_f32.hip): fp32 operands on v_mfma_f32_16x16x4_f32, the same dropout hashes
+_FlashAttnF32Fn = _flash_attn_fn("_FlashAttnF32Fn", torch.float32, "attn_f32_fwd", "attn_f32_bwd", keep_lo=False)
 
 
 def _compute_dtype(qkv: torch.Tensor):

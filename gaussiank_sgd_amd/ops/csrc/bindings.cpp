@@ -1823,11 +1823,12 @@ void emb_backward(at::Tensor ids, c10::optional<at::Tensor> tt, at::Tensor dx, c
                    (int)T, (int)P, (int)NT, (int)H, cur_stream(ids));
 }
 
-// fused self-attention (attn.hip)
-void check_attn(const at::Tensor& t, const char* name, int64_t rows, int64_t cols) {
-  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16 && t.is_contiguous() && t.numel() == rows * cols &&
+// fused self-attention (attn.hip: bf16, attn_f32.hip: fp32)
+void check_attn(const at::Tensor& t, at::ScalarType dt, const char* name, int64_t rows, int64_t cols) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == dt && t.is_contiguous() && t.numel() == rows * cols &&
                   reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
-              name, " must be a contiguous 16-byte aligned bf16 GPU tensor of ", rows, " x ", cols, " elements");
+              name, " must be a contiguous 16-byte aligned ", dt == at::kFloat ? "fp32" : "bf16", " GPU tensor of ",
+              rows, " x ", cols, " elements");
 }
 
 void check_attn_f32(const at::Tensor& t, const char* name, int64_t n) {
@@ -1835,7 +1836,7 @@ void check_attn_f32(const at::Tensor& t, const char* name, int64_t n) {
               name, " must be a contiguous fp32 GPU tensor of ", n, " elements");
 }
 
-// packed key mask: int32 [B, T / 32] on qkv's device (kernels/attn_mask.h); null when absent
+// packed key mask: int32 [B, T / 32] on qkv's device (kernels/attn_common.h); null when absent
 const uint32_t* key_bits_ptr(const c10::optional<at::Tensor>& t, const at::Tensor& qkv, int64_t B, int64_t T) {
   if (!t.has_value() || !t->defined()) return nullptr;
   TORCH_CHECK(t->is_cuda() && t->device() == qkv.device() && t->scalar_type() == at::kInt && t->is_contiguous() &&
@@ -1849,85 +1850,76 @@ void* out_lo_ptr(const c10::optional<at::Tensor>& t, const uint32_t* key_bits, b
                  int64_t cols) {
   if (!t.has_value() || !t->defined()) return nullptr;
   TORCH_CHECK(key_bits != nullptr || causal, "out_lo needs key_bits or causal (only the masked kernels take it)");
-  check_attn(*t, "out_lo", rows, cols);
+  check_attn(*t, at::kBFloat16, "out_lo", rows, cols);
   return t->data_ptr();
+}
+
+// What the four attention ops check, for tensors of element type dt: qkv, out and lse, and in a backward
+// call dout, delta and dqkv too.  Gives B, T and the key bits (null without a mask).
+struct AttnCall {
+  int64_t B, T;
+  const uint32_t* key_bits;
+};
+
+AttnCall check_attn_call(at::ScalarType dt, const at::Tensor& qkv, const at::Tensor& out, const at::Tensor& lse,
+                         int64_t heads, double p, const c10::optional<at::Tensor>& key_bits,
+                         const at::Tensor* dout = nullptr, const at::Tensor* delta = nullptr,
+                         const at::Tensor* dqkv = nullptr) {
+  TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == 3 * heads * 64, "qkv: [B, T, 3 * heads * 64]");
+  const int64_t B = qkv.size(0), T = qkv.size(1);
+  TORCH_CHECK(dt == at::kFloat ? gk::attn_f32_supported((int)T, 64) : gk::attn_supported((int)T, 64),
+              dt == at::kFloat ? "attn_f32" : "attn", ": T must be a multiple of 128");
+  check_attn(qkv, dt, "qkv", B * T, 3 * heads * 64);
+  check_attn(out, dt, "out", B * T, heads * 64);
+  check_attn_f32(lse, "lse", B * heads * T);
+  if (dout != nullptr) {
+    check_attn(*dqkv, dt, "dqkv", B * T, 3 * heads * 64);
+    check_attn(*dout, dt, "dout", B * T, heads * 64);
+    check_attn_f32(*delta, "delta", B * heads * T);
+  }
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "attn: dropout p in [0, 1)");
+  // the kernels index the dropout pair hash, (bh * T + q) * T / 2 + key / 2, in 32 bits
+  TORCH_CHECK(B * heads * T * (T / 2) < (int64_t(1) << 32), "attn: dropout hash index must fit 32 bits");
+  return {B, T, key_bits_ptr(key_bits, qkv, B, T)};
 }
 
 void attn_fwd(at::Tensor qkv, at::Tensor out, at::Tensor lse, int64_t heads, double p, int64_t seed,
               c10::optional<at::Tensor> seed_dev, c10::optional<at::Tensor> key_bits,
               c10::optional<at::Tensor> out_lo, bool causal) {
-  TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == 3 * heads * 64, "qkv: [B, T, 3 * heads * 64]");
-  const int64_t B = qkv.size(0), T = qkv.size(1);
-  TORCH_CHECK(gk::attn_supported((int)T, 64), "attn: T must be a multiple of 128");
-  check_attn(qkv, "qkv", B * T, 3 * heads * 64);
-  check_attn(out, "out", B * T, heads * 64);
-  check_attn_f32(lse, "lse", B * heads * T);
-  TORCH_CHECK(p >= 0.0 && p < 1.0, "attn: dropout p in [0, 1)");
-  const uint32_t* kb = key_bits_ptr(key_bits, qkv, B, T);
+  const AttnCall c = check_attn_call(at::kBFloat16, qkv, out, lse, heads, p, key_bits);
+  void* lo = out_lo_ptr(out_lo, c.key_bits, causal, c.B * c.T, heads * 64);
   c10::DeviceGuard guard(qkv.device());
-  gk::attn_fwd(qkv.data_ptr(), out.data_ptr(), lse.data_ptr<float>(), (int)B, (int)T, (int)heads, (float)p,
-               (uint32_t)seed, seed_word(seed_dev), kb, out_lo_ptr(out_lo, kb, causal, B * T, heads * 64), causal,
-               cur_stream(qkv));
+  gk::attn_fwd(qkv.data_ptr(), out.data_ptr(), lse.data_ptr<float>(), (int)c.B, (int)c.T, (int)heads, (float)p,
+               (uint32_t)seed, seed_word(seed_dev), c.key_bits, lo, causal, cur_stream(qkv));
 }
 
 void attn_bwd(at::Tensor qkv, at::Tensor out, at::Tensor dout, at::Tensor lse, at::Tensor delta, at::Tensor dqkv,
               int64_t heads, double p, int64_t seed, c10::optional<at::Tensor> seed_dev,
               c10::optional<at::Tensor> key_bits, c10::optional<at::Tensor> out_lo, bool causal) {
-  TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == 3 * heads * 64, "qkv: [B, T, 3 * heads * 64]");
-  const int64_t B = qkv.size(0), T = qkv.size(1);
-  TORCH_CHECK(gk::attn_supported((int)T, 64), "attn: T must be a multiple of 128");
-  check_attn(qkv, "qkv", B * T, 3 * heads * 64);
-  check_attn(dqkv, "dqkv", B * T, 3 * heads * 64);
-  check_attn(out, "out", B * T, heads * 64);
-  check_attn(dout, "dout", B * T, heads * 64);
-  check_attn_f32(lse, "lse", B * heads * T);
-  check_attn_f32(delta, "delta", B * heads * T);
-  const uint32_t* kb = key_bits_ptr(key_bits, qkv, B, T);
+  const AttnCall c = check_attn_call(at::kBFloat16, qkv, out, lse, heads, p, key_bits, &dout, &delta, &dqkv);
+  const void* lo = out_lo_ptr(out_lo, c.key_bits, causal, c.B * c.T, heads * 64);
   c10::DeviceGuard guard(qkv.device());
   gk::attn_bwd(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr<float>(), delta.data_ptr<float>(),
-               dqkv.data_ptr(), (int)B, (int)T, (int)heads, (float)p, (uint32_t)seed, seed_word(seed_dev), kb,
-               out_lo_ptr(out_lo, kb, causal, B * T, heads * 64), causal, cur_stream(qkv));
-}
-
-void check_attn32(const at::Tensor& t, const char* name, int64_t rows, int64_t cols) {
-  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() == rows * cols &&
-                  reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
-              name, " must be a contiguous 16-byte aligned fp32 GPU tensor of ", rows, " x ", cols, " elements");
+               dqkv.data_ptr(), (int)c.B, (int)c.T, (int)heads, (float)p, (uint32_t)seed, seed_word(seed_dev),
+               c.key_bits, lo, causal, cur_stream(qkv));
 }
 
 void attn_f32_fwd(at::Tensor qkv, at::Tensor out, at::Tensor lse, int64_t heads, double p, int64_t seed,
                   c10::optional<at::Tensor> seed_dev, c10::optional<at::Tensor> key_bits, bool causal) {
-  TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == 3 * heads * 64, "qkv: [B, T, 3 * heads * 64]");
-  const int64_t B = qkv.size(0), T = qkv.size(1);
-  TORCH_CHECK(gk::attn_f32_supported((int)T, 64), "attn_f32: T must be a multiple of 128");
-  check_attn32(qkv, "qkv", B * T, 3 * heads * 64);
-  check_attn32(out, "out", B * T, heads * 64);
-  check_attn_f32(lse, "lse", B * heads * T);
-  TORCH_CHECK(p >= 0.0 && p < 1.0, "attn: dropout p in [0, 1)");
-  TORCH_CHECK(B * heads * T * (T / 2) < (int64_t(1) << 32), "attn: dropout hash index must fit 32 bits");
-  const uint32_t* kb = key_bits_ptr(key_bits, qkv, B, T);
+  const AttnCall c = check_attn_call(at::kFloat, qkv, out, lse, heads, p, key_bits);
   c10::DeviceGuard guard(qkv.device());
-  gk::attn_f32_fwd(qkv.data_ptr<float>(), out.data_ptr<float>(), lse.data_ptr<float>(), (int)B, (int)T, (int)heads,
-                   (float)p, (uint32_t)seed, seed_word(seed_dev), kb, causal, cur_stream(qkv));
+  gk::attn_f32_fwd(qkv.data_ptr<float>(), out.data_ptr<float>(), lse.data_ptr<float>(), (int)c.B, (int)c.T,
+                   (int)heads, (float)p, (uint32_t)seed, seed_word(seed_dev), c.key_bits, causal, cur_stream(qkv));
 }
 
 void attn_f32_bwd(at::Tensor qkv, at::Tensor out, at::Tensor dout, at::Tensor lse, at::Tensor delta, at::Tensor dqkv,
                   int64_t heads, double p, int64_t seed, c10::optional<at::Tensor> seed_dev,
                   c10::optional<at::Tensor> key_bits, bool causal) {
-  TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == 3 * heads * 64, "qkv: [B, T, 3 * heads * 64]");
-  const int64_t B = qkv.size(0), T = qkv.size(1);
-  TORCH_CHECK(gk::attn_f32_supported((int)T, 64), "attn_f32: T must be a multiple of 128");
-  check_attn32(qkv, "qkv", B * T, 3 * heads * 64);
-  check_attn32(dqkv, "dqkv", B * T, 3 * heads * 64);
-  check_attn32(out, "out", B * T, heads * 64);
-  check_attn32(dout, "dout", B * T, heads * 64);
-  check_attn_f32(lse, "lse", B * heads * T);
-  check_attn_f32(delta, "delta", B * heads * T);
-  const uint32_t* kb = key_bits_ptr(key_bits, qkv, B, T);
+  const AttnCall c = check_attn_call(at::kFloat, qkv, out, lse, heads, p, key_bits, &dout, &delta, &dqkv);
   c10::DeviceGuard guard(qkv.device());
   gk::attn_f32_bwd(qkv.data_ptr<float>(), out.data_ptr<float>(), dout.data_ptr<float>(), lse.data_ptr<float>(),
-                   delta.data_ptr<float>(), dqkv.data_ptr<float>(), (int)B, (int)T, (int)heads, (float)p,
-                   (uint32_t)seed, seed_word(seed_dev), kb, causal, cur_stream(qkv));
+                   delta.data_ptr<float>(), dqkv.data_ptr<float>(), (int)c.B, (int)c.T, (int)heads, (float)p,
+                   (uint32_t)seed, seed_word(seed_dev), c.key_bits, causal, cur_stream(qkv));
 }
 
 // [B, T] key mask (nonzero = valid; any 1-, 2-, 4- or 8-byte dtype) -> packed bits int32 [B, T / 32]

@@ -27,10 +27,7 @@
 //    kernel) is pre-scaled by c once, and the row constants are the MFMA's
 //    initial accumulator: S = c q.k - m (forward), c q.k - lse and
 //    dZ - delta (backward), so p = exp2(S) needs no per-score arithmetic;
-//  - the forward rescales its running max lazily: only when some row's tile
-//    max exceeds the current m by 8 (log2 units, so p <= 256) does the wave
-//    take the textbook update (cross-lane row max, O and l rescale).  The
-//    first tile always takes it, so m starts at the first tile's row max;
+//  - the forward rescales its running max lazily (attn_common.h);
 //  - one 32-bit hash per PAIR of keys gives both dropout uniforms (16 bits
 //    each); the dK/dV kernel (keys on lanes) splits the pair's hashes between
 //    neighbour lanes and swaps them with a DPP quad permute.
@@ -39,52 +36,20 @@
 // (aswz) that is conflict-free both for the 16-row ds_read_b128 operand reads
 // and for the 8-row transposed reads, so Q / K tiles serve both.
 //
-// Dropout: keep(query, key) = half (key & 1) of hash(seed, (bh*T + q)*T/2 +
-// key/2) >= round(p * 65536), in all three kernels and attn_dropout_mask (for
-// tests); the mask is regenerated, never stored.
-//
-// Key-padding mask (MASK instantiations, attn_mask.h): packed valid bits per
-// (batch, key); masked keys get the score -inf, so P is exactly 0, lse runs
-// over the valid keys, and dK / dV of masked keys are written as zeros.  The
-// forward and the dQ kernel skip the arithmetic of key tiles without a valid
-// key and stop at the last tile that has one; the dK/dV kernel returns early
-// for 128 masked keys.  Every skip is uniform over the workgroup (or, inside
-// the dK/dV loop, leaves the wave on its barriers and staging duty).  The
-// masked forward can also store what the bf16 rounding of the output dropped
-// (out_lo), which the dQ kernel adds back for delta = rowsum(dO * O): rows
-// with few valid keys have concentrated P, where dP and delta nearly cancel.
-// The MASK = false instantiations are the code without any of this.
-//
-// Causal mask (CAUSAL instantiations): query q sees key k iff k <= q, ANDed
-// with the key bits under MASK.  The forward and the dQ kernel stop at tile
-// 2 qb + 2 (the last one their query 128 qb + 127 sees); per wave a tile is
-// fully visible (no mask work), diagonal (masked element-wise through the
-// accumulator init, attn_mask.h) or past the wave's last query (waves 0 and 1
-// on the workgroup's last tile: arithmetic skipped, barrier and staging kept).
-// The dK/dV kernel starts its query tiles at 2 kb; waves 2 and 3 skip the
-// arithmetic of that tile.  Every case is wave-uniform.  The forward's lazy
-// running max is then kept per row: a row below the threshold does not move
-// its m when another row of the wave does, so nothing a later query sees
-// changes an earlier row's bits, and under MASK a row whose scores have all
-// been -inf so far (left padding) waits for its first finite one; a query
-// without any visible valid key gives out = 0, lse = 0 and zero dQ.  out_lo is
-// kept as under MASK: the first rows of a sequence see few keys.
-// The CAUSAL = false instantiations are the code without any of this.
+// Dropout, the key-padding mask (MASK instantiations, with out_lo) and the
+// causal mask (CAUSAL instantiations): attn_common.h, shared with attn_f32.hip.
 #include "common.h"
 #include "gk_kernels.h"
 #include "mfma_util.h"
-#include "attn_mask.h"
+#include "attn_common.h"
 
 namespace gk {
 namespace {
 
-constexpr int kHD = 64;                 // head dim
-constexpr int kKT = 64;                 // rows per LDS tile (keys, or queries in the dK/dV kernel)
-constexpr int kTileB = kKT * kHD * 2;   // 8 KiB
+constexpr int kTileB = kKT * kHD * 2;   // 8 KiB per [kKT rows][kHD] tile
 constexpr int kAW = 4;                  // waves per workgroup, 32 rows each
-constexpr int kRows = 32 * kAW;         // rows per workgroup
+static_assert(kRows == 32 * kAW, "rows per workgroup");
 constexpr int kPieces = 16 / kAW;       // 1-KiB LDS-DMA pieces per wave per tile pair
-constexpr float kLazy = 8.f;            // forward: rescale when a row max grows by more than this (log2)
 constexpr int kStages = 3;              // LDS ring: tiles t+1 and t+2 in flight while t is consumed
 
 // chunk swizzle of a [rows][128 B] tile (chunk c of row r at c ^ aswz(r)):
@@ -95,18 +60,6 @@ constexpr int kStages = 3;              // LDS ring: tiles t+1 and t+2 in flight
 // (r >> 1) & 7 map leaves both reads 2-way)
 __device__ __forceinline__ int aswz(int r) { return (((r >> 2) & 1) << 1) | (((r >> 1) & 1) << 2); }
 __device__ __forceinline__ int aoff(int r, int c) { return r * 128 + ((c ^ aswz(r)) << 4); }
-
-__device__ __forceinline__ float fexp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-// Workgroups are dispatched round-robin over the 8 XCDs (each with its own
-// L2): give every XCD a contiguous range of logical blocks, so the row blocks
-// of one (batch, head) -- which all stream the same K / V (or Q / dO) -- run
-// on one XCD and share its L2 instead of fetching them once per XCD.
-__device__ __forceinline__ int xcd_block() {
-  const int n = gridDim.x, b = blockIdx.x;
-  if (n % 8) return b;
-  return (b & 7) * (n >> 3) + (b >> 3);
-}
 
 // wait until the LDS-DMA of the current tile has landed: only the next
 // tile's N pieces (issued after it) may still be in flight
@@ -119,9 +72,6 @@ __device__ __forceinline__ void wait_tile(bool last) {
 __device__ __forceinline__ int ring_next(int b) { return b + 1 == kStages ? 0 : b + 1; }
 
 __device__ __forceinline__ uint32_t lds_addr(const void* p) { return (uint32_t)(uintptr_t)(GK_LDS const char*)p; }
-
-// dropout uniforms of keys (2j, 2j + 1) of one (bh, query)
-__device__ __forceinline__ uint32_t pair_hash(uint32_t seed, uint32_t pidx) { return hash_u32(pidx, seed); }
 
 // this wave's LDS-DMA sources for two [rows][64] matrices staged as tiles
 // (a: pieces 0..7, b: 8..15) -- row r0 is added per tile
@@ -203,36 +153,7 @@ __device__ __forceinline__ bf16x8 scale_bf16x8(const bf16x8& x, float s) {
   return __builtin_bit_cast(bf16x8, w);
 }
 
-__device__ __forceinline__ f32x4 splat4(float v) { return f32x4{v, v, v, v}; }
-
-struct AttnArgs {
-  const uint16_t* qkv;
-  const uint16_t* out;
-  const uint16_t* dout;
-  uint16_t* o;        // forward output
-  uint16_t* dqkv;
-  float* lse;
-  float* delta;
-  int T, H;
-  float sc;           // log2(e) / sqrt(64)
-  float qscale;       // 1 / sqrt(64)
-  float dscale;       // 1 / (1 - p_effective)
-  uint32_t thr;       // drop threshold on 16 hash bits
-  uint32_t seed;
-  const uint32_t* key_bits;   // optional [B, T / 32] valid-key bits (attn_mask.h), MASK kernels only
-  // optional, MASK kernels only: what the bf16 rounding of the output dropped, out_lo = bf16(O - out)
-  // [B, T, H, 64], written by the forward and added back by the dQ kernel for delta
-  uint16_t* out_lo;
-  // optional replay word (graph capture): the effective seed mixes it in, so
-  // a replayed step draws a fresh mask while forward and backward of one
-  // replay read the same word
-  const uint32_t* seed_dev;
-};
-
-__device__ __forceinline__ uint32_t eff_seed(const AttnArgs& a) {
-  if (a.seed_dev == nullptr) return a.seed;
-  return hash_u32(__builtin_amdgcn_readfirstlane(*a.seed_dev), a.seed);
-}
+using AttnArgs = AttnArgsT<uint16_t>;
 
 // ---------------------------------------------------------------------------
 // forward: one workgroup = 4 waves x 32 queries of one (batch, head); K/V
@@ -245,16 +166,8 @@ __global__ void __launch_bounds__(64 * kAW, (MASK || CAUSAL) ? 3 : 2) attn_fwd_k
   const uint32_t seed = DROP ? eff_seed(a) : 0u;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, g = lane >> 4;
   const int T = a.T, H = a.H;
-  const int nqb = T / kRows;
   int bh, qb;
-  if constexpr (CAUSAL) {   // heaviest row blocks first (attn_mask.h)
-    causal_block(nqb, bh, qb);
-    qb = nqb - 1 - qb;
-  } else {
-    const int blk = xcd_block();
-    bh = blk / nqb;
-    qb = blk - bh * nqb;
-  }
+  attn_block<CAUSAL, true>(T / kRows, bh, qb);
   const int b = bh / H, h = bh - b * H;
   const uint32_t* kbits = MASK ? a.key_bits + (int64_t)b * (T >> 5) : nullptr;
   const int64_t ld = 3LL * H * kHD;
@@ -264,11 +177,8 @@ __global__ void __launch_bounds__(64 * kAW, (MASK || CAUSAL) ? 3 : 2) attn_fwd_k
   DmaSrc dma;
   dma.init(base + (int64_t)(H + h) * kHD, ld, base + (int64_t)(2 * H + h) * kHD, ld, wave, lane);
   const int64_t tstep = kKT * ld;
-  // MASK: stop after the last tile with a valid key (0 tiles: an empty sequence)
-  const int ntm = MASK ? mask_tiles(kbits, T >> 5, lane) : T / kKT;
-  // CAUSAL: and after the workgroup's last visible tile, the one of its query 128 qb + 127
-  const int nt = CAUSAL ? min(ntm, 2 * qb + 2) : ntm;
-  const int q0u = CAUSAL ? __builtin_amdgcn_readfirstlane(q0) : 0;   // wave-uniform: the tile cases below
+  const int nt = key_tiles<MASK, CAUSAL>(kbits, T, qb, lane);
+  const int q0u = CAUSAL ? __builtin_amdgcn_readfirstlane(q0) : 0;   // wave-uniform: the tile cases (TileMask)
 
   bf16x8 qf[2][2];
 #pragma unroll
@@ -298,45 +208,25 @@ __global__ void __launch_bounds__(64 * kAW, (MASK || CAUSAL) ? 3 : 2) attn_fwd_k
   const uint32_t lbase = lds_addr(smem);
 
   int cur = 0, pre = 2;   // ring slots of tile t and of tile t + 2
-  bool started = false;   // MASK: a tile with a valid key has been seen
-  // CAUSAL && MASK: the row has had no finite score yet.  Left padding or a hole over keys 0 .. q leaves a
-  // row's first tiles all -inf; such a row does not move m and takes the first-tile step at its first
-  // finite score (a row that never has one ends with l = 0: out = 0, lse = 0)
-  bool fresh[2] = {true, true};
+  bool started = false, fresh[2] = {true, true};   // first_tile(), softmax_step()
+  TileMask<MASK, CAUSAL> tm;
   for (int t = 0; t < nt; ++t) {
-    uint32_t w0 = ~0u, w1 = ~0u;   // valid bits of the tile's 64 keys (workgroup-uniform)
-    if (MASK) {
-      w0 = kbits[2 * t];
-      w1 = kbits[2 * t + 1];
-    }
+    tm.load(kbits, t);
     wait_tile<kPieces>(t + 1 >= nt);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     if (t + 2 < nt) dma.issue((t + 2) * tstep, (t + 2) * tstep, lds + pre * 2 * kTileB, wave);
-    // CAUSAL, per wave: the tile is fully visible (qrel >= 63), diagonal, or past the wave's last query
-    // (qrel < -31: waves 0 and 1 on the workgroup's last tile)
-    const int qrel = CAUSAL ? q0u - kKT * t : 0;
-    // no valid / no visible key: the ring moves on, the arithmetic is skipped (the wave has passed the
-    // tile's barrier and staged its pieces)
-    if ((MASK && (w0 | w1) == 0u) || (CAUSAL && qrel < -31)) {
+    // skipped tile: the ring moves on (the wave has passed the tile's barrier and staged its pieces)
+    if (tm.skip(q0u, t)) {
       cur = ring_next(cur);
       pre = ring_next(pre);
       continue;
     }
     const char* Ks = smem + cur * 2 * kTileB;
 
-    // S^T - m (log2 units), the running max as the initial accumulator (MASK:
-    // -inf for a masked key, which the MFMA carries through; set before the
-    // operand reads so that the tile's arithmetic stays one scheduling region)
+    // S^T - m (log2 units), the running max as the initial accumulator
     f32x4 s[2][4];
-    if (MASK || CAUSAL) {
-#pragma unroll
-      for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt) s[qt][kt] = splat4(-m[qt]);
-      if (MASK && (w0 & w1) != ~0u) mask_scores_t(s, w0 >> (4 * g), w1 >> (4 * g));
-      if (CAUSAL && qrel < 63) causal_scores_t(s, qrel + li - 4 * g);
-    }
+    if (MASK || CAUSAL) tm.init(s, {-m[0], -m[1]}, li, g);
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt) {
       const bf16x8 k0 = *reinterpret_cast<const bf16x8*>(Ks + aoff(16 * kt + li, g));
@@ -345,62 +235,10 @@ __global__ void __launch_bounds__(64 * kAW, (MASK || CAUSAL) ? 3 : 2) attn_fwd_k
       for (int qt = 0; qt < 2; ++qt)
         s[qt][kt] = mfma(k1, qf[qt][1], mfma(k0, qf[qt][0], (MASK || CAUSAL) ? s[qt][kt] : splat4(-m[qt])));
     }
-    // the first tile (MASK: the first with a valid key, where every row has a finite max; CAUSAL alone:
-    // tile 0, key 0 is visible to every query; CAUSAL && MASK: per row, fresh[])
-    const bool first = MASK ? !started : t == 0;
-    started = true;
-
+    const bool first = first_tile<MASK>(started, t);
 #pragma unroll
-    for (int qt = 0; qt < 2; ++qt) {
-      float mx = fmaxf(fmaxf(s[qt][0][0], s[qt][0][1]), fmaxf(s[qt][0][2], s[qt][0][3]));
-#pragma unroll
-      for (int kt = 1; kt < 4; ++kt)
-        mx = fmaxf(mx, fmaxf(fmaxf(s[qt][kt][0], s[qt][kt][1]), fmaxf(s[qt][kt][2], s[qt][kt][3])));
-      // wave-uniform, rare after the first tile
-      if ((CAUSAL && MASK) ? __ballot(fresh[qt] || mx > kLazy) != 0 : first || __ballot(mx > kLazy) != 0) {
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        float d;
-        if constexpr (CAUSAL) {
-          // per row: a row below the threshold keeps its m bit for bit (d = 0 changes nothing), so what
-          // another row of the wave scores -- a later query sees keys this one does not -- cannot reach it
-          const bool fr = MASK ? fresh[qt] : first;
-          const bool dark = MASK && mx == -INFINITY;   // no finite score in this tile
-          d = fr ? (dark ? 0.f : mx) : (mx > kLazy ? mx : 0.f);
-          if (MASK) fresh[qt] = fr && dark;
-        } else {
-          d = first ? mx : fmaxf(mx, 0.f);
-        }
-        m[qt] += d;
-        const float al = fexp2(-d);
-        l[qt] *= al;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) o[qt][dt] *= al;
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt) s[qt][kt] -= splat4(d);
-      }
-      float ls = 0.f;
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt) {
-        uint32_t hh[2];
-        if (DROP) {
-          const uint32_t pi = hrow[qt] + t * (kKT / 2) + 8 * kt;
-          hh[0] = pair_hash(seed, pi);
-          hh[1] = pair_hash(seed, pi + 1);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float p = fexp2(s[qt][kt][r]);
-          ls += p;
-          if (DROP) {
-            const uint32_t u = (r & 1) ? hh[r >> 1] >> 16 : hh[r >> 1] & 0xffffu;
-            p = u >= a.thr ? p : 0.f;
-          }
-          s[qt][kt][r] = p;
-        }
-      }
-      l[qt] += ls;
-    }
+    for (int qt = 0; qt < 2; ++qt)
+      softmax_step<DROP, MASK, CAUSAL>(s[qt], o[qt], m[qt], l[qt], fresh[qt], first, hrow[qt], t, seed, a.thr);
 
     const uint32_t vb = lbase + cur * 2 * kTileB + kTileB;
     cur = ring_next(cur);
@@ -431,14 +269,8 @@ __global__ void __launch_bounds__(64 * kAW, (MASK || CAUSAL) ? 3 : 2) attn_fwd_k
   if (MASK && nt == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // tile 0's LDS-DMA
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
-    float lt = l[qt];
-    lt += __shfl_xor(lt, 16, 64);
-    lt += __shfl_xor(lt, 32, 64);
     const int q = q0 + 16 * qt + li;
-    // MASK, a sequence without a valid key: out = 0 and lse = 0 (no tile was waited for)
-    const bool none = MASK && lt == 0.f;
-    if (g == 0) a.lse[(int64_t)bh * T + q] = none ? 0.f : m[qt] + __log2f(lt);
-    const float inv = none ? 0.f : a.dscale / lt;
+    const float inv = finish_row<MASK>(l[qt], m[qt], a.dscale, a.lse + (int64_t)bh * T + q, g);
     uint16_t* op = a.o + ((int64_t)b * T + q) * (H * kHD) + h * kHD + 4 * g;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) store4(op + 16 * dt, o[qt][dt], inv);
@@ -461,16 +293,8 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_dq_kernel(AttnArgs a) {
   const uint32_t seed = DROP ? eff_seed(a) : 0u;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, g = lane >> 4;
   const int T = a.T, H = a.H;
-  const int nqb = T / kRows;
   int bh, qb;
-  if constexpr (CAUSAL) {   // heaviest row blocks first (attn_mask.h)
-    causal_block(nqb, bh, qb);
-    qb = nqb - 1 - qb;
-  } else {
-    const int blk = xcd_block();
-    bh = blk / nqb;
-    qb = blk - bh * nqb;
-  }
+  attn_block<CAUSAL, true>(T / kRows, bh, qb);
   const int b = bh / H, h = bh - b * H;
   const uint32_t* kbits = MASK ? a.key_bits + (int64_t)b * (T >> 5) : nullptr;
   const int64_t ld = 3LL * H * kHD, ldo = (int64_t)H * kHD;
@@ -480,9 +304,7 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_dq_kernel(AttnArgs a) {
   DmaSrc dma;
   dma.init(base + (int64_t)(H + h) * kHD, ld, base + (int64_t)(2 * H + h) * kHD, ld, wave, lane);
   const int64_t tstep = kKT * ld;
-  // MASK: stop after the last tile with a valid key (0 tiles: an empty sequence)
-  const int ntm = MASK ? mask_tiles(kbits, T >> 5, lane) : T / kKT;
-  const int nt = CAUSAL ? min(ntm, 2 * qb + 2) : ntm;   // CAUSAL: the forward's tile count and tile cases
+  const int nt = key_tiles<MASK, CAUSAL>(kbits, T, qb, lane);   // the forward's tile count and tile cases
   const int q0u = CAUSAL ? __builtin_amdgcn_readfirstlane(q0) : 0;
 
   bf16x8 qf[2][2], df[2][2], of[2][2];
@@ -541,20 +363,15 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_dq_kernel(AttnArgs a) {
   const uint32_t lbase = lds_addr(smem);
 
   int cur = 0, pre = 2;   // ring slots of tile t and of tile t + 2
+  TileMask<MASK, CAUSAL> tm;
   for (int t = 0; t < nt; ++t) {
-    uint32_t w0 = ~0u, w1 = ~0u;   // valid bits of the tile's 64 keys (workgroup-uniform)
-    if (MASK) {
-      w0 = kbits[2 * t];
-      w1 = kbits[2 * t + 1];
-    }
+    tm.load(kbits, t);
     // the delta stores follow tile 1's pieces: drain everything on the first tile
     wait_tile<kPieces>(t == 0 || t + 1 >= nt);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     if (t + 2 < nt) dma.issue((t + 2) * tstep, (t + 2) * tstep, lds + pre * 2 * kTileB, wave);
-    const int qrel = CAUSAL ? q0u - kKT * t : 0;   // as in the forward
-    // no valid / no visible key: P = 0 for the whole tile
-    if ((MASK && (w0 | w1) == 0u) || (CAUSAL && qrel < -31)) {
+    if (tm.skip(q0u, t)) {
       cur = ring_next(cur);
       pre = ring_next(pre);
       continue;
@@ -563,15 +380,7 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_dq_kernel(AttnArgs a) {
     const char* Vs = Ks + kTileB;
 
     f32x4 s[2][4], dz[2][4];
-    // masked / hidden keys: -inf through the MFMA, so P = exp2(-inf) and with it dS are exactly 0
-    if (MASK || CAUSAL) {
-#pragma unroll
-      for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt) s[qt][kt] = splat4(nlse[qt]);
-      if (MASK && (w0 & w1) != ~0u) mask_scores_t(s, w0 >> (4 * g), w1 >> (4 * g));
-      if (CAUSAL && qrel < 63) causal_scores_t(s, qrel + li - 4 * g);
-    }
+    if (MASK || CAUSAL) tm.init(s, nlse, li, g);
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt) {
       const bf16x8 k0 = *reinterpret_cast<const bf16x8*>(Ks + aoff(16 * kt + li, g));
@@ -585,27 +394,7 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_dq_kernel(AttnArgs a) {
       }
     }
 
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt) {
-        uint32_t hh[2];
-        if (DROP) {
-          const uint32_t pi = hrow[qt] + t * (kKT / 2) + 8 * kt;
-          hh[0] = pair_hash(seed, pi);
-          hh[1] = pair_hash(seed, pi + 1);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float p = fexp2(s[qt][kt][r]);
-          float dd = dz[qt][kt][r];   // dP - delta (no dropout)
-          if (DROP) {
-            const uint32_t u = (r & 1) ? hh[r >> 1] >> 16 : hh[r >> 1] & 0xffffu;
-            dd = u >= a.thr ? dd * a.dscale : -del[qt];
-          }
-          s[qt][kt][r] = p * dd;
-        }
-      }
+    ds_step<DROP>(s, dz, del, hrow, t, seed, a.thr, a.dscale);
 
     const uint32_t kb = lbase + cur * 2 * kTileB;
     cur = ring_next(cur);
@@ -658,15 +447,8 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_kv_kernel(AttnArgs a) {
   const uint32_t seed = DROP ? eff_seed(a) : 0u;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, g = lane >> 4;
   const int T = a.T, H = a.H;
-  const int nkb = T / kRows;
   int bh, kb;
-  if constexpr (CAUSAL) {   // heaviest key blocks (the first ones) first (attn_mask.h)
-    causal_block(nkb, bh, kb);
-  } else {
-    const int blk = xcd_block();
-    bh = blk / nkb;
-    kb = blk - bh * nkb;
-  }
+  attn_block<CAUSAL, false>(T / kRows, bh, kb);
   const int b = bh / H, h = bh - b * H;
   const int64_t ld = 3LL * H * kHD, ldo = (int64_t)H * kHD;
   const uint16_t* base = a.qkv + (int64_t)b * T * ld;
@@ -896,47 +678,17 @@ __global__ void __launch_bounds__(256) attn_pack_key_mask_kernel(const E* __rest
   if ((lane & 31) == 0 && k < T) bits[(int64_t)row * (T >> 5) + w] = (uint32_t)(bal >> (lane & 32));
 }
 
-AttnArgs make_args(int T, int H, float p, uint32_t seed, const uint32_t* seed_dev) {
-  AttnArgs a{};
-  a.seed_dev = seed_dev;
-  a.T = T;
-  a.H = H;
-  a.qscale = 0.125f;                       // 1 / sqrt(64)
-  a.sc = 1.4426950408889634f * 0.125f;     // log2(e) / sqrt(64)
-  uint32_t thr = p > 0.f ? (uint32_t)lrintf(p * 65536.f) : 0u;
-  if (thr > 65535u) thr = 65535u;
-  a.thr = thr;
-  a.dscale = thr ? 65536.f / (float)(65536u - thr) : 1.f;
-  a.seed = seed;
-  return a;
+void launch_fwd(const AttnArgs& a, bool causal, dim3 grid, hipStream_t stream) {
+  attn_dispatch(a.thr != 0, a.key_bits != nullptr, causal, [&](auto d, auto m, auto c) {
+    hipLaunchKernelGGL((attn_fwd_kernel<d(), m(), c()>), grid, dim3(64 * kAW), 0, stream, a);
+  });
 }
 
-template <bool CAUSAL>
-void launch_fwd(const AttnArgs& a, dim3 grid, hipStream_t stream) {
-  if (a.key_bits) {
-    if (a.thr) hipLaunchKernelGGL((attn_fwd_kernel<true, true, CAUSAL>), grid, dim3(64 * kAW), 0, stream, a);
-    else hipLaunchKernelGGL((attn_fwd_kernel<false, true, CAUSAL>), grid, dim3(64 * kAW), 0, stream, a);
-  } else if (a.thr) hipLaunchKernelGGL((attn_fwd_kernel<true, false, CAUSAL>), grid, dim3(64 * kAW), 0, stream, a);
-  else hipLaunchKernelGGL((attn_fwd_kernel<false, false, CAUSAL>), grid, dim3(64 * kAW), 0, stream, a);
-}
-
-template <bool CAUSAL>
-void launch_bwd(const AttnArgs& a, dim3 grid, hipStream_t stream) {
-  if (a.key_bits) {
-    if (a.thr) {
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<true, true, CAUSAL>), grid, dim3(64 * kAW), 0, stream, a);
-      hipLaunchKernelGGL((attn_bwd_kv_kernel<true, true, CAUSAL>), grid, dim3(64 * kAW), 0, stream, a);
-    } else {
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<false, true, CAUSAL>), grid, dim3(64 * kAW), 0, stream, a);
-      hipLaunchKernelGGL((attn_bwd_kv_kernel<false, true, CAUSAL>), grid, dim3(64 * kAW), 0, stream, a);
-    }
-  } else if (a.thr) {
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<true, false, CAUSAL>), grid, dim3(64 * kAW), 0, stream, a);
-    hipLaunchKernelGGL((attn_bwd_kv_kernel<true, false, CAUSAL>), grid, dim3(64 * kAW), 0, stream, a);
-  } else {
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<false, false, CAUSAL>), grid, dim3(64 * kAW), 0, stream, a);
-    hipLaunchKernelGGL((attn_bwd_kv_kernel<false, false, CAUSAL>), grid, dim3(64 * kAW), 0, stream, a);
-  }
+void launch_bwd(const AttnArgs& a, bool causal, dim3 grid, hipStream_t stream) {
+  attn_dispatch(a.thr != 0, a.key_bits != nullptr, causal, [&](auto d, auto m, auto c) {
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<d(), m(), c()>), grid, dim3(64 * kAW), 0, stream, a);
+    hipLaunchKernelGGL((attn_bwd_kv_kernel<d(), m(), c()>), grid, dim3(64 * kAW), 0, stream, a);
+  });
 }
 
 }  // namespace
@@ -945,21 +697,20 @@ bool attn_supported(int T, int D) { return D == kHD && T >= kRows && T % kRows =
 
 void attn_fwd(const void* qkv, void* out, float* lse, int B, int T, int H, float p, uint32_t seed,
               const uint32_t* seed_dev, const uint32_t* key_bits, void* out_lo, bool causal, hipStream_t stream) {
-  AttnArgs a = make_args(T, H, p, seed, seed_dev);
+  AttnArgs a = make_args<uint16_t>(T, H, p, seed, seed_dev);
   a.out_lo = (key_bits || causal) ? static_cast<uint16_t*>(out_lo) : nullptr;
   a.qkv = static_cast<const uint16_t*>(qkv);
   a.o = static_cast<uint16_t*>(out);
   a.lse = lse;
   a.key_bits = key_bits;
   const dim3 grid((unsigned)(B * H * (T / kRows)));
-  if (causal) launch_fwd<true>(a, grid, stream);
-  else launch_fwd<false>(a, grid, stream);
+  launch_fwd(a, causal, grid, stream);
 }
 
 void attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int B,
               int T, int H, float p, uint32_t seed, const uint32_t* seed_dev, const uint32_t* key_bits,
               const void* out_lo, bool causal, hipStream_t stream) {
-  AttnArgs a = make_args(T, H, p, seed, seed_dev);
+  AttnArgs a = make_args<uint16_t>(T, H, p, seed, seed_dev);
   a.key_bits = key_bits;
   a.out_lo = (key_bits || causal) ? static_cast<uint16_t*>(const_cast<void*>(out_lo)) : nullptr;
   a.qkv = static_cast<const uint16_t*>(qkv);
@@ -969,8 +720,7 @@ void attn_bwd(const void* qkv, const void* out, const void* dout, const float* l
   a.delta = delta;
   a.dqkv = static_cast<uint16_t*>(dqkv);
   const dim3 grid((unsigned)(B * H * (T / kRows)));
-  if (causal) launch_bwd<true>(a, grid, stream);
-  else launch_bwd<false>(a, grid, stream);
+  launch_bwd(a, causal, grid, stream);
 }
 
 void attn_pack_key_mask(const void* mask, int elem_size, bool is_float, uint32_t* bits, int B, int T,
@@ -995,7 +745,7 @@ void attn_pack_key_mask(const void* mask, int elem_size, bool is_float, uint32_t
 
 void attn_dropout_mask(uint8_t* mask, int B, int H, int T, float p, uint32_t seed, const uint32_t* seed_dev,
                        hipStream_t stream) {
-  const AttnArgs a = make_args(T, H, p, seed, seed_dev);
+  const AttnArgs a = make_args<uint16_t>(T, H, p, seed, seed_dev);
   const int64_t npairs = (int64_t)B * H * T * T / 2;
   hipLaunchKernelGGL(attn_dropout_mask_kernel, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, stream, mask,
                      npairs, a, a.thr);

@@ -7,9 +7,8 @@
 //
 // I/O layouts (fp32), as attn.hip: qkv / dqkv [B, T, 3, heads, 64], out / dout
 // [B, T, heads, 64], lse [B, heads, T] (log2 domain), delta [B, heads, T].
-// Dropout: the same pair hashes as attn.hip (keep(query, key) = half (key & 1)
-// of hash(seed, (bh*T + q)*T/2 + key/2) >= round(p * 65536)), so
-// ops/attention.dropout_mask describes both precisions.
+// Dropout: the same pair hashes as attn.hip, so ops/attention.dropout_mask
+// describes both precisions.
 //
 // MFMA v_mfma_f32_16x16x4_f32, lane = 16 g + li: operand A[i][k] -> lane
 // (i = li, k = g), B[k][j] -> lane (k = g, j = li), D[i][j] -> lane holds
@@ -33,38 +32,26 @@
 // staged by LDS-DMA (global_load_lds 16 B per lane; the swizzle is applied to
 // the source address), two stages deep.
 //
-// Key-padding mask (MASK instantiations), as attn.hip: masked keys score
-// -inf; the forward and the dQ kernel skip the arithmetic of key tiles without
-// a valid key and stop at the last tile that has one; the dK/dV kernel writes
-// zeros and returns for 128 masked keys.  MASK = false is the code without it.
-//
-// Causal mask (CAUSAL instantiations), as attn.hip: the forward and the dQ
-// kernel stop at tile 2 qb + 2 and mask the wave's diagonal tile element-wise,
-// waves 0 and 1 skip the arithmetic of the last tile; the dK/dV kernel starts
-// at query tile 2 kb (an even tile, so the two stages keep their parity); the
-// forward's lazy running max is kept per row.  CAUSAL = false is the code
-// without it.
+// Dropout, the key-padding mask (MASK instantiations; no out_lo: the fp32
+// output has no rounding residue worth keeping) and the causal mask (CAUSAL
+// instantiations; the dK/dV kernel starts at an even query tile, so the two
+// stages keep their parity): attn_common.h, shared with attn.hip.
 #include "common.h"
 #include "gk_kernels.h"
 #include "mfma_util.h"
-#include "attn_mask.h"
+#include "attn_common.h"
 
 namespace gk {
 namespace {
 
-constexpr int kHD = 64;                     // head dim
-constexpr int kKT = 64;                     // rows per LDS tile
-constexpr int kFTile = kKT * kHD * 4;       // 16 KiB
+constexpr int kFTile = kKT * kHD * 4;       // 16 KiB per [kKT rows][kHD] tile
 constexpr int kWaves = 4;                   // 32 rows per wave
-constexpr int kRows = 32 * kWaves;          // rows per workgroup
-constexpr float kLazy = 8.f;                // forward: rescale when a row max grows by more than this (log2)
+static_assert(kRows == 32 * kWaves, "rows per workgroup");
 
 __device__ __forceinline__ uint32_t foff(int r, int c) { return (uint32_t)(r * 256 + ((c ^ (r & 15)) << 4)); }
 // byte offset of element (r, col) (ds_read_b32)
 __device__ __forceinline__ uint32_t foff1(int r, int col) { return foff(r, col >> 2) + ((col & 3) << 2); }
 
-__device__ __forceinline__ float fexp2(float x) { return __builtin_amdgcn_exp2f(x); }
-__device__ __forceinline__ f32x4 splat4(float v) { return f32x4{v, v, v, v}; }
 __device__ __forceinline__ f32x4 mfma4(float a, float b, const f32x4& c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
@@ -76,34 +63,7 @@ __device__ __forceinline__ f32x4 mfma16(const f32x4& a, const f32x4& b, f32x4 c)
   return mfma4(a[3], b[3], c);
 }
 
-__device__ __forceinline__ int xcd_block() {
-  const int n = gridDim.x, b = blockIdx.x;
-  if (n % 8) return b;
-  return (b & 7) * (n >> 3) + (b >> 3);
-}
-
-struct AttnF32Args {
-  const float* qkv;
-  const float* out;
-  const float* dout;
-  float* o;
-  float* dqkv;
-  float* lse;
-  float* delta;
-  int T, H;
-  float sc;        // log2(e) / sqrt(64)
-  float qscale;    // 1 / sqrt(64)
-  float dscale;    // 1 / (1 - p_effective)
-  uint32_t thr;    // drop threshold on 16 hash bits
-  uint32_t seed;
-  const uint32_t* seed_dev;
-  const uint32_t* key_bits;   // optional [B, T / 32] valid-key bits (attn_mask.h), MASK kernels only
-};
-
-__device__ __forceinline__ uint32_t eff_seed(const AttnF32Args& a) {
-  if (a.seed_dev == nullptr) return a.seed;
-  return hash_u32(__builtin_amdgcn_readfirstlane(*a.seed_dev), a.seed);
-}
+using AttnF32Args = AttnArgsT<float>;
 
 // this wave's 4 LDS-DMA pieces (1 KiB = 4 rows each) of a [64][64] fp32 tile
 // whose row 0 is at src (row stride ld floats): pieces 4 wave .. 4 wave + 3
@@ -139,16 +99,8 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Arg
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int li = lane & 15, g = lane >> 4;
   const int T = a.T, H = a.H;
-  const int nqb = T / kRows;
   int bh, qb;
-  if constexpr (CAUSAL) {   // heaviest row blocks first (attn_mask.h)
-    causal_block(nqb, bh, qb);
-    qb = nqb - 1 - qb;
-  } else {
-    const int blk = xcd_block();
-    bh = blk / nqb;
-    qb = blk - bh * nqb;
-  }
+  attn_block<CAUSAL, true>(T / kRows, bh, qb);
   const int b = bh / H, h = bh - b * H;
   const int64_t ld = 3LL * H * kHD;
   const float* base = a.qkv + (int64_t)b * T * ld;
@@ -162,10 +114,7 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Arg
 
   dk.issue(0, lds, wave);
   dv.issue(0, lds + kFTile, wave);
-  // MASK: stop after the last tile with a valid key (0 tiles: an empty sequence)
-  const int ntm = MASK ? mask_tiles(kbits, T >> 5, lane) : T / kKT;
-  // CAUSAL: and after the workgroup's last visible tile, the one of its query 128 qb + 127
-  const int nt = CAUSAL ? min(ntm, 2 * qb + 2) : ntm;
+  const int nt = key_tiles<MASK, CAUSAL>(kbits, T, qb, lane);
   f32x4 qf[2][4];
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt)
@@ -184,17 +133,10 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Arg
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) hrow[qt] = ((uint32_t)bh * T + q0 + 16 * qt + li) * (uint32_t)(T >> 1) + 2 * g;
 
-  bool started = false;   // MASK: a tile with a valid key has been seen
-  // CAUSAL && MASK: the row has had no finite score yet.  Left padding or a hole over keys 0 .. q leaves a
-  // row's first tiles all -inf; such a row does not move m and takes the first-tile step at its first
-  // finite score (a row that never has one ends with l = 0: out = 0, lse = 0)
-  bool fresh[2] = {true, true};
+  bool started = false, fresh[2] = {true, true};   // first_tile(), softmax_step()
+  TileMask<MASK, CAUSAL> tm;
   for (int t = 0; t < nt; ++t) {
-    uint32_t w0 = ~0u, w1 = ~0u;   // valid bits of the tile's 64 keys (workgroup-uniform)
-    if (MASK) {
-      w0 = kbits[2 * t];
-      w1 = kbits[2 * t + 1];
-    }
+    tm.load(kbits, t);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of tile t
     __builtin_amdgcn_s_barrier();                        // everyone's pieces; tile t - 1 consumed
     __builtin_amdgcn_sched_barrier(0);
@@ -205,21 +147,11 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Arg
       dk.issue((t + 1) * tstep, nx, wave);
       dv.issue((t + 1) * tstep, nx + kFTile, wave);
     }
-    // CAUSAL, per wave (wave-uniform): the tile is fully visible (qrel >= 63), diagonal, or past the wave's
-    // last query (qrel < -31: waves 0 and 1 on the workgroup's last tile)
-    const int qrel = CAUSAL ? q0 - kKT * t : 0;
-    // no valid / no visible key: staged and waited for, no arithmetic
-    if ((MASK && (w0 | w1) == 0u) || (CAUSAL && qrel < -31)) continue;
+    if (tm.skip(q0, t)) continue;   // q0 is wave-uniform (wave is)
 
     // S^T - m (log2 units)
     f32x4 s[2][4];
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt) s[qt][kt] = splat4(-m[qt]);
-    // masked keys: -inf in the initial accumulator, which the MFMAs carry through
-    if (MASK && (w0 & w1) != ~0u) mask_scores_t(s, w0 >> (4 * g), w1 >> (4 * g));
-    if (CAUSAL && qrel < 63) causal_scores_t(s, qrel + li - 4 * g);
+    tm.init(s, {-m[0], -m[1]}, li, g);
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
@@ -228,61 +160,10 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Arg
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt) s[qt][kt] = mfma16(kv, qf[qt][c], s[qt][kt]);
       }
-    // the first tile (MASK: the first with a valid key, where every row has a finite max; CAUSAL alone:
-    // tile 0, key 0 is visible to every query; CAUSAL && MASK: per row, fresh[])
-    const bool first = MASK ? !started : t == 0;
-    started = true;
-
+    const bool first = first_tile<MASK>(started, t);
 #pragma unroll
-    for (int qt = 0; qt < 2; ++qt) {
-      float mx = fmaxf(fmaxf(s[qt][0][0], s[qt][0][1]), fmaxf(s[qt][0][2], s[qt][0][3]));
-#pragma unroll
-      for (int kt = 1; kt < 4; ++kt)
-        mx = fmaxf(mx, fmaxf(fmaxf(s[qt][kt][0], s[qt][kt][1]), fmaxf(s[qt][kt][2], s[qt][kt][3])));
-      if ((CAUSAL && MASK) ? __ballot(fresh[qt] || mx > kLazy) != 0 : first || __ballot(mx > kLazy) != 0) {
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        float d;
-        if constexpr (CAUSAL) {
-          // per row: a row below the threshold keeps its m bit for bit (d = 0 changes nothing), so what
-          // another row of the wave scores -- a later query sees keys this one does not -- cannot reach it
-          const bool fr = MASK ? fresh[qt] : first;
-          const bool dark = MASK && mx == -INFINITY;   // no finite score in this tile
-          d = fr ? (dark ? 0.f : mx) : (mx > kLazy ? mx : 0.f);
-          if (MASK) fresh[qt] = fr && dark;
-        } else {
-          d = first ? mx : fmaxf(mx, 0.f);
-        }
-        m[qt] += d;
-        const float al = fexp2(-d);
-        l[qt] *= al;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) o[qt][dt] *= al;
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt) s[qt][kt] -= splat4(d);
-      }
-      float ls = 0.f;
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt) {
-        uint32_t hh[2];
-        if (DROP) {
-          const uint32_t pi = hrow[qt] + t * (kKT / 2) + 8 * kt;
-          hh[0] = hash_u32(pi, seed);
-          hh[1] = hash_u32(pi + 1, seed);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float p = fexp2(s[qt][kt][r]);
-          ls += p;
-          if (DROP) {
-            const uint32_t u = (r & 1) ? hh[r >> 1] >> 16 : hh[r >> 1] & 0xffffu;
-            p = u >= a.thr ? p : 0.f;
-          }
-          s[qt][kt][r] = p;
-        }
-      }
-      l[qt] += ls;
-    }
+    for (int qt = 0; qt < 2; ++qt)
+      softmax_step<DROP, MASK, CAUSAL>(s[qt], o[qt], m[qt], l[qt], fresh[qt], first, hrow[qt], t, seed, a.thr);
 
     // O^T += V^T P^T: MFMA j contracts keys 16 kt + 4g + j
 #pragma unroll
@@ -302,14 +183,8 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Arg
   if (MASK && nt == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // tile 0's LDS-DMA
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
-    float lt = l[qt];
-    lt += __shfl_xor(lt, 16, 64);
-    lt += __shfl_xor(lt, 32, 64);
     const int q = q0 + 16 * qt + li;
-    // MASK, a sequence without a valid key: out = 0 and lse = 0 (no tile was waited for)
-    const bool none = MASK && lt == 0.f;
-    if (g == 0) a.lse[(int64_t)bh * T + q] = none ? 0.f : m[qt] + __log2f(lt);
-    const float inv = none ? 0.f : a.dscale / lt;
+    const float inv = finish_row<MASK>(l[qt], m[qt], a.dscale, a.lse + (int64_t)bh * T + q, g);
     float* op = a.o + ((int64_t)b * T + q) * (H * kHD) + h * kHD + 4 * g;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<f32x4*>(op + 16 * dt) = o[qt][dt] * inv;
@@ -327,16 +202,8 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_dq_kernel(AttnF32
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int li = lane & 15, g = lane >> 4;
   const int T = a.T, H = a.H;
-  const int nqb = T / kRows;
   int bh, qb;
-  if constexpr (CAUSAL) {   // heaviest row blocks first (attn_mask.h)
-    causal_block(nqb, bh, qb);
-    qb = nqb - 1 - qb;
-  } else {
-    const int blk = xcd_block();
-    bh = blk / nqb;
-    qb = blk - bh * nqb;
-  }
+  attn_block<CAUSAL, true>(T / kRows, bh, qb);
   const int b = bh / H, h = bh - b * H;
   const int64_t ld = 3LL * H * kHD, ldo = (int64_t)H * kHD;
   const float* base = a.qkv + (int64_t)b * T * ld;
@@ -350,10 +217,7 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_dq_kernel(AttnF32
 
   dk.issue(0, lds, wave);
   dv.issue(0, lds + kFTile, wave);
-  // MASK: stop after the last tile with a valid key (0 tiles: an empty sequence)
-  const int ntm = MASK ? mask_tiles(kbits, T >> 5, lane) : T / kKT;
-  // CAUSAL: and after the workgroup's last visible tile, the one of its query 128 qb + 127
-  const int nt = CAUSAL ? min(ntm, 2 * qb + 2) : ntm;
+  const int nt = key_tiles<MASK, CAUSAL>(kbits, T, qb, lane);
   f32x4 qf[2][4], df[2][4];
   float nlse[2], del[2], ndel[2];
   uint32_t hrow[2];
@@ -385,12 +249,9 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_dq_kernel(AttnF32
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) dq[qt][dt] = splat4(0.f);
 
+  TileMask<MASK, CAUSAL> tm;
   for (int t = 0; t < nt; ++t) {
-    uint32_t w0 = ~0u, w1 = ~0u;   // valid bits of the tile's 64 keys (workgroup-uniform)
-    if (MASK) {
-      w0 = kbits[2 * t];
-      w1 = kbits[2 * t + 1];
-    }
+    tm.load(kbits, t);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
@@ -401,21 +262,14 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_dq_kernel(AttnF32
       dk.issue((t + 1) * tstep, nx, wave);
       dv.issue((t + 1) * tstep, nx + kFTile, wave);
     }
-    const int qrel = CAUSAL ? q0 - kKT * t : 0;   // as in the forward
-    // no valid / no visible key: P = 0 for the whole tile
-    if ((MASK && (w0 | w1) == 0u) || (CAUSAL && qrel < -31)) continue;
+    if (tm.skip(q0, t)) continue;
 
     f32x4 s[2][4], dz[2][4];
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
-      for (int kt = 0; kt < 4; ++kt) {
-        s[qt][kt] = splat4(nlse[qt]);
-        dz[qt][kt] = splat4(ndel[qt]);
-      }
-    // masked keys: -inf through the MFMAs, so P = exp2(-inf) and with it dS are exactly 0
-    if (MASK && (w0 & w1) != ~0u) mask_scores_t(s, w0 >> (4 * g), w1 >> (4 * g));
-    if (CAUSAL && qrel < 63) causal_scores_t(s, qrel + li - 4 * g);
+      for (int kt = 0; kt < 4; ++kt) dz[qt][kt] = splat4(ndel[qt]);
+    tm.init(s, nlse, li, g);
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt) {
 #pragma unroll
@@ -431,27 +285,7 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_dq_kernel(AttnF32
       __builtin_amdgcn_sched_barrier(0);   // one key tile's operand reads in flight at a time (VGPRs)
     }
 
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt) {
-        uint32_t hh[2];
-        if (DROP) {
-          const uint32_t pi = hrow[qt] + t * (kKT / 2) + 8 * kt;
-          hh[0] = hash_u32(pi, seed);
-          hh[1] = hash_u32(pi + 1, seed);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float p = fexp2(s[qt][kt][r]);
-          float dd = dz[qt][kt][r];   // dP - delta (no dropout)
-          if (DROP) {
-            const uint32_t u = (r & 1) ? hh[r >> 1] >> 16 : hh[r >> 1] & 0xffffu;
-            dd = u >= a.thr ? dd * a.dscale : -del[qt];
-          }
-          s[qt][kt][r] = p * dd;
-        }
-      }
+    ds_step<DROP>(s, dz, del, hrow, t, seed, a.thr, a.dscale);
 
     // dQ^T += K^T dS^T: MFMA j contracts keys 16 kt + 4g + j
 #pragma unroll
@@ -494,15 +328,8 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_kv_kernel(AttnF32
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int li = lane & 15, g = lane >> 4;
   const int T = a.T, H = a.H;
-  const int nkb = T / kRows;
   int bh, kb;
-  if constexpr (CAUSAL) {   // heaviest key blocks (the first ones) first (attn_mask.h)
-    causal_block(nkb, bh, kb);
-  } else {
-    const int blk = xcd_block();
-    bh = blk / nkb;
-    kb = blk - bh * nkb;
-  }
+  attn_block<CAUSAL, false>(T / kRows, bh, kb);
   const int b = bh / H, h = bh - b * H;
   const int64_t ld = 3LL * H * kHD, ldo = (int64_t)H * kHD;
   const float* base = a.qkv + (int64_t)b * T * ld;
@@ -617,7 +444,7 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_kv_kernel(AttnF32
           float z = p, d2 = dz[kt][r];   // dP - delta (no dropout)
           if (DROP) {
             const uint32_t qg = (uint32_t)(t * kKT + qr + r);
-            const uint32_t hv = hash_u32(hbase + qg * (uint32_t)(T >> 1) + (uint32_t)((k0 + 16 * kt + li) >> 1), seed);
+            const uint32_t hv = pair_hash(seed, hbase + qg * (uint32_t)(T >> 1) + (uint32_t)((k0 + 16 * kt + li) >> 1));
             const bool keep = __builtin_amdgcn_ubfe(hv, hsh, 16) >= a.thr;
             z = keep ? p * a.dscale : 0.f;
             d2 = keep ? d2 * a.dscale : -del4[r];
@@ -658,53 +485,24 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_kv_kernel(AttnF32
   }
 }
 
-AttnF32Args make_args(int T, int H, float p, uint32_t seed, const uint32_t* seed_dev) {
-  AttnF32Args a{};
-  a.seed_dev = seed_dev;
-  a.T = T;
-  a.H = H;
-  a.qscale = 0.125f;                       // 1 / sqrt(64)
-  a.sc = 1.4426950408889634f * 0.125f;     // log2(e) / sqrt(64)
-  uint32_t thr = p > 0.f ? (uint32_t)lrintf(p * 65536.f) : 0u;
-  if (thr > 65535u) thr = 65535u;
-  a.thr = thr;
-  a.dscale = thr ? 65536.f / (float)(65536u - thr) : 1.f;
-  a.seed = seed;
-  return a;
-}
-
+// K: a kernel template instantiation; lds: its dynamic LDS (above the 64 KiB a launch gets unasked)
 template <typename K>
 void launch(K kern, int nblocks, int lds, const AttnF32Args& a, hipStream_t stream) {
   hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(64 * kWaves), lds, stream, a);
 }
 
-template <bool CAUSAL>
-void launch_fwd(int nb, const AttnF32Args& a, hipStream_t stream) {
-  if (a.key_bits) {
-    if (a.thr) launch(attn_f32_fwd_kernel<true, true, CAUSAL>, nb, 4 * kFTile, a, stream);
-    else launch(attn_f32_fwd_kernel<false, true, CAUSAL>, nb, 4 * kFTile, a, stream);
-  } else if (a.thr) launch(attn_f32_fwd_kernel<true, false, CAUSAL>, nb, 4 * kFTile, a, stream);
-  else launch(attn_f32_fwd_kernel<false, false, CAUSAL>, nb, 4 * kFTile, a, stream);
+void launch_fwd(int nb, const AttnF32Args& a, bool causal, hipStream_t stream) {
+  attn_dispatch(a.thr != 0, a.key_bits != nullptr, causal, [&](auto d, auto m, auto c) {
+    launch(attn_f32_fwd_kernel<d(), m(), c()>, nb, 4 * kFTile, a, stream);
+  });
 }
 
-template <bool CAUSAL>
-void launch_bwd(int nb, const AttnF32Args& a, hipStream_t stream) {
-  if (a.key_bits) {
-    if (a.thr) {
-      launch(attn_f32_bwd_dq_kernel<true, true, CAUSAL>, nb, 4 * kFTile, a, stream);
-      launch(attn_f32_bwd_kv_kernel<true, true, CAUSAL>, nb, 2 * kKvStage, a, stream);
-    } else {
-      launch(attn_f32_bwd_dq_kernel<false, true, CAUSAL>, nb, 4 * kFTile, a, stream);
-      launch(attn_f32_bwd_kv_kernel<false, true, CAUSAL>, nb, 2 * kKvStage, a, stream);
-    }
-  } else if (a.thr) {
-    launch(attn_f32_bwd_dq_kernel<true, false, CAUSAL>, nb, 4 * kFTile, a, stream);
-    launch(attn_f32_bwd_kv_kernel<true, false, CAUSAL>, nb, 2 * kKvStage, a, stream);
-  } else {
-    launch(attn_f32_bwd_dq_kernel<false, false, CAUSAL>, nb, 4 * kFTile, a, stream);
-    launch(attn_f32_bwd_kv_kernel<false, false, CAUSAL>, nb, 2 * kKvStage, a, stream);
-  }
+void launch_bwd(int nb, const AttnF32Args& a, bool causal, hipStream_t stream) {
+  attn_dispatch(a.thr != 0, a.key_bits != nullptr, causal, [&](auto d, auto m, auto c) {
+    launch(attn_f32_bwd_dq_kernel<d(), m(), c()>, nb, 4 * kFTile, a, stream);
+    launch(attn_f32_bwd_kv_kernel<d(), m(), c()>, nb, 2 * kKvStage, a, stream);
+  });
 }
 
 }  // namespace
@@ -713,20 +511,19 @@ bool attn_f32_supported(int T, int D) { return D == kHD && T >= kRows && T % kRo
 
 void attn_f32_fwd(const float* qkv, float* out, float* lse, int B, int T, int H, float p, uint32_t seed,
                   const uint32_t* seed_dev, const uint32_t* key_bits, bool causal, hipStream_t stream) {
-  AttnF32Args a = make_args(T, H, p, seed, seed_dev);
+  AttnF32Args a = make_args<float>(T, H, p, seed, seed_dev);
   a.qkv = qkv;
   a.o = out;
   a.lse = lse;
   a.key_bits = key_bits;
   const int nb = B * H * (T / kRows);
-  if (causal) launch_fwd<true>(nb, a, stream);
-  else launch_fwd<false>(nb, a, stream);
+  launch_fwd(nb, a, causal, stream);
 }
 
 void attn_f32_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* delta, float* dqkv,
                   int B, int T, int H, float p, uint32_t seed, const uint32_t* seed_dev, const uint32_t* key_bits,
                   bool causal, hipStream_t stream) {
-  AttnF32Args a = make_args(T, H, p, seed, seed_dev);
+  AttnF32Args a = make_args<float>(T, H, p, seed, seed_dev);
   a.qkv = qkv;
   a.out = out;
   a.dout = dout;
@@ -735,8 +532,7 @@ void attn_f32_bwd(const float* qkv, const float* out, const float* dout, const f
   a.dqkv = dqkv;
   a.key_bits = key_bits;
   const int nb = B * H * (T / kRows);
-  if (causal) launch_bwd<true>(nb, a, stream);
-  else launch_bwd<false>(nb, a, stream);
+  launch_bwd(nb, a, causal, stream);
 }
 
 }  // namespace gk

@@ -300,6 +300,26 @@ def test_causal_false_is_the_existing_call(dtype, p, masked):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("Bq,heads", [(1, 2), (2, 2), (2, 4)])
+def test_causal_grid_classes(Bq, heads, dtype):
+    """The workgroup -> (batch, head, row block) mapping (attn_common.h) at T = 256, two row blocks per
+    (batch, head): a grid of 4 (not a multiple of 8: no XCD remap), of 8 (the remap, with the causal order
+    falling back to one range) and of 16 (whole (batch, head)s per XCD).  A block computed twice leaves
+    another one's NaN pre-fill.  Keys 64..127 (a whole tile) masked, the last sequence right-padded too;
+    p = 0.1, so the hash index follows the mapping as well."""
+    from gaussiank_sgd_amd.ops import attention
+    T, p = 256, 0.1
+    qkv, dout = _qkv(T, 61, dtype, heads)[:Bq], _dout(T, dtype, heads)[:Bq]
+    m = torch.ones(Bq, T, dtype=torch.bool, device="cuda")
+    m[:, 64:128] = False
+    m[-1, 200:] = False
+    want = _reference(qkv, p, 91, m, dout, heads)
+    got = _raw(qkv, p, 91, attention.pack_key_mask(m), dout, fill=float("nan"), heads=heads)
+    _check(got, want, heads)
+    assert bool((got[2].view(Bq, T, 3, heads, 64)[:, :, 1:][~m] == 0).all())
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("p", PS)
 def test_causal_deterministic(dtype, p):
     from gaussiank_sgd_amd.ops import attention

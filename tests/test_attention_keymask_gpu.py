@@ -215,6 +215,25 @@ def test_holes(dtype, p):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("B,heads", [(1, 2), (2, 2), (2, 4)])
+def test_grid_classes(B, heads, dtype):
+    """The workgroup -> (batch, head, row block) mapping (attn_common.h) at T = 256, two row blocks per
+    (batch, head): a grid of 4 (not a multiple of 8: no XCD remap), of 8 and of 16 (the remap).  A block
+    computed twice leaves another one's NaN pre-fill.  Keys 64..127 (a whole tile) masked, the last sequence
+    right-padded too; p = 0.1, so the hash index follows the mapping as well.
+    test_attention_causal_gpu.py::test_causal_grid_classes is the causal twin."""
+    from gaussiank_sgd_amd.ops import attention
+    T, p = 256, 0.1
+    qkv, dout = _qkv(B, T, heads, 61, dtype), _dout(B, T, heads, dtype)
+    m = torch.ones(B, T, dtype=torch.bool, device="cuda")
+    m[:, 64:128] = False
+    m[-1, 200:] = False
+    got = _raw(qkv, heads, p, 91, attention.pack_key_mask(m), dout, fill=float("nan"))
+    _check(got, _reference(qkv, heads, p, 91, m, dout), heads)
+    assert _masked_kv_zero(got[2], m, heads)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("p", PS)
 def test_masked_keys_dkv_are_written(dtype, p):
     """T = 128: one workgroup per head, keys 32..63 (a whole wave) masked."""
