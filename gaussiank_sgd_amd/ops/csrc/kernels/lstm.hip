@@ -366,11 +366,8 @@ void lstm_rec_gemm_x6(const float* A, int64_t lda, const uint16_t* B3, int64_t l
                       int N, int K, int S, hipStream_t stream) {
   if (M <= 0 || N <= 0 || S <= 0) return;
   dim3 grid((unsigned)(N / 64), (unsigned)S, (unsigned)ceil_div(M, 128));
-  const int ks = K / S;
-  if (ks % 64 == 0)
-    hipLaunchKernelGGL(rec_gemm_x6_kernel<2>, grid, dim3(kBlock), 0, stream, A, lda, B3, ldb, bplane, P, M, N, ks);
-  else
-    hipLaunchKernelGGL(rec_gemm_x6_kernel<1>, grid, dim3(kBlock), 0, stream, A, lda, B3, ldb, bplane, P, M, N, ks);
+  // K % (64 S) == 0 (checked on the host): every slice is whole batches of D = 2
+  hipLaunchKernelGGL(rec_gemm_x6_kernel<2>, grid, dim3(kBlock), 0, stream, A, lda, B3, ldb, bplane, P, M, N, K / S);
 }
 
 template <typename T>

@@ -166,17 +166,6 @@ def split3(w: torch.Tensor) -> torch.Tensor:
     return torch.stack([hi, mid, lo]).contiguous()
 
 
-def _splits(kblocks: int, nblocks: int, target: int = 512) -> int:
-    """K-slice count S for the split-K step GEMM: the largest divisor of the
-    64-deep K-block count keeping S * nblocks <= target workgroups (two per
-    CU) and every slice >= two K-blocks deep."""
-    best = 1
-    for d in range(2, kblocks + 1):
-        if kblocks % d == 0 and d * nblocks <= target and kblocks // d >= 2:
-            best = d
-    return best
-
-
 class _LSTMLayerFn(torch.autograd.Function):
     """One LSTM layer over a whole sequence (one autograd node: the step loop
     lives inside forward / backward)."""
