@@ -445,6 +445,9 @@ void clip_grad_norm(at::Tensor g, double max_norm, at::Tensor ws, at::Tensor coe
 // ---------------------------------------------------------------------------
 // fused batch norm + add + relu (channels-last)
 // ---------------------------------------------------------------------------
+// Every op: validate, build the argument structs of gk_kernels.h, DeviceGuard, call.
+bool has(const OptTensor& t) { return t.has_value() && t->defined(); }
+
 int64_t channels_of(const at::Tensor& x) { return x.dim() == 4 ? x.size(1) : x.size(-1); }
 
 void check_cl(const at::Tensor& t, const char* name) {
@@ -457,26 +460,103 @@ void check_cl(const at::Tensor& t, const char* name) {
   TORCH_CHECK(t.scalar_type() == at::kBFloat16 || t.scalar_type() == at::kFloat, name, " must be bf16 or fp32");
 }
 
-const float* opt_f32(const c10::optional<at::Tensor>& t) {
-  if (!t.has_value() || !t->defined()) return nullptr;
-  TORCH_CHECK(t->scalar_type() == at::kFloat && t->is_contiguous() && t->is_cuda(), "expected fp32 GPU tensor");
-  return t->data_ptr<float>();
+// x viewed as [M, C]: channels-last, bf16 or fp32, a channel count the kernels take
+gk::BnShape bn_shape(const at::Tensor& x) {
+  check_cl(x, "x");
+  const int64_t C = channels_of(x);
+  const int eb = (int)x.element_size();
+  TORCH_CHECK(gk::bn_supported((int)C, eb), "channel count not supported by the fused kernel");
+  return {x.numel() / C, (int)C, eb};
 }
 
-float* opt_f32_mut(const c10::optional<at::Tensor>& t) { return const_cast<float*>(opt_f32(t)); }
+// activations of x's layout, dtype and element count
+void check_same(const at::Tensor& x, std::initializer_list<const at::Tensor*> ts, const char* names) {
+  for (const at::Tensor* t : ts) {
+    check_cl(*t, names);
+    TORCH_CHECK(t->scalar_type() == x.scalar_type() && t->numel() == x.numel(), names,
+                " must have x's dtype and element count");
+  }
+}
 
-// optional tensor that must have `ref`'s dtype, shape and channels-last layout
-const void* opt_like(const c10::optional<at::Tensor>& t, const at::Tensor& ref, const char* name) {
-  if (!t.has_value() || !t->defined()) return nullptr;
-  check_cl(*t, name);
-  TORCH_CHECK(t->scalar_type() == ref.scalar_type() && t->sizes() == ref.sizes(), name, " must match dy");
+// optional activation of x's layout, dtype and element count
+void* opt_same(const at::Tensor& x, const OptTensor& t, const char* name) {
+  if (!has(t)) return nullptr;
+  check_same(x, {&*t}, name);
   return t->data_ptr();
 }
 
-int64_t* opt_i64(const c10::optional<at::Tensor>& t) {
-  if (!t.has_value() || !t->defined()) return nullptr;
+// optional second gradient: dy's dtype, shape and channels-last layout
+const void* opt_dy2(const OptTensor& dy2, const at::Tensor& dy) {
+  if (!has(dy2)) return nullptr;
+  check_cl(*dy2, "dy2");
+  TORCH_CHECK(dy2->scalar_type() == dy.scalar_type() && dy2->sizes() == dy.sizes(), "dy2 must match dy");
+  return dy2->data_ptr();
+}
+
+// per-channel buffers: fp32[C] on the GPU
+void check_channel_bufs(std::initializer_list<const at::Tensor*> ts, int C, const char* names) {
+  for (const at::Tensor* t : ts)
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous() && t->numel() >= C, names,
+                " must be contiguous fp32[C] GPU tensors");
+}
+
+float* opt_channel_buf(const OptTensor& t, int C, const char* name) {
+  if (!has(t)) return nullptr;
+  check_channel_bufs({&*t}, C, name);
+  return t->data_ptr<float>();
+}
+
+int64_t* opt_i64(const OptTensor& t) {
+  if (!has(t)) return nullptr;
   TORCH_CHECK(t->scalar_type() == at::kLong && t->numel() == 1 && t->is_cuda(), "expected int64[1] GPU tensor");
   return t->data_ptr<int64_t>();
+}
+
+gk::BnFwdStats fwd_stats(const OptTensor& w, const OptTensor& b, const OptTensor& run_mean, const OptTensor& run_var,
+                         const at::Tensor& save_mean, const at::Tensor& save_invstd, const at::Tensor& scale,
+                         const at::Tensor& shift, double eps, double momentum, const OptTensor& nbt, int C) {
+  check_channel_bufs({&save_mean, &save_invstd, &scale, &shift}, C, "save_mean / save_invstd / scale / shift");
+  TORCH_CHECK(has(run_mean) == has(run_var), "run_mean and run_var go together");
+  return {opt_channel_buf(w, C, "w"), opt_channel_buf(b, C, "b"), (float)eps, (float)momentum,
+          opt_channel_buf(run_mean, C, "run_mean"), opt_channel_buf(run_var, C, "run_var"),
+          save_mean.data_ptr<float>(), save_invstd.data_ptr<float>(), scale.data_ptr<float>(),
+          shift.data_ptr<float>(), opt_i64(nbt)};
+}
+
+gk::BnBwdStats bwd_stats(const OptTensor& w, const at::Tensor& mean, const at::Tensor& invstd,
+                         const at::Tensor& dgamma, const at::Tensor& dbeta, const OptTensor& gw_acc,
+                         const OptTensor& gb_acc, int C) {
+  check_channel_bufs({&mean, &invstd, &dgamma, &dbeta}, C, "mean / invstd / dgamma / dbeta");
+  return {opt_channel_buf(w, C, "w"), mean.data_ptr<float>(), invstd.data_ptr<float>(), dgamma.data_ptr<float>(),
+          dbeta.data_ptr<float>(), opt_channel_buf(gw_acc, C, "gw_acc"), opt_channel_buf(gb_acc, C, "gb_acc")};
+}
+
+// fp32 [2, rows, C] partials of a producer's epilogue; the finalize reads rows [0, used) of each half
+gk::BnPartials partials(const at::Tensor& t, int64_t used, int C, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.dim() == 3 && t.size(0) == 2 &&
+                  t.size(2) == C && used > 0 && used <= t.size(1),
+              name, " must be fp32 [2, rows, C] partials with 0 < used rows <= rows");
+  const float* p = t.data_ptr<float>();
+  return {p, p + t.size(1) * C, (int)used};
+}
+
+gk::BnPartials partials(const OptTensor& t, int64_t used, int C, const char* name) {
+  return has(t) ? partials(*t, used, C, name) : gk::BnPartials{};
+}
+
+uint8_t* relu_mask(const OptTensor& mask, bool relu, gk::BnShape sh) {
+  if (!relu) return nullptr;
+  TORCH_CHECK(has(mask) && mask->is_cuda() && mask->scalar_type() == at::kByte &&
+                  mask->numel() >= (int64_t)gk::bn_mask_bytes(sh.M, sh.C, sh.elem_bytes),
+              "mask: relu needs a uint8 GPU tensor of bn_mask_bytes");
+  return mask->data_ptr<uint8_t>();
+}
+
+float* check_ws(const at::Tensor& ws, gk::BnShape sh) {
+  TORCH_CHECK(ws.is_cuda() && ws.scalar_type() == at::kFloat &&
+                  ws.numel() >= (int64_t)gk::bn_workspace_floats(sh.M, sh.C, sh.elem_bytes),
+              "ws: a fp32 GPU tensor of bn_workspace_floats");
+  return ws.data_ptr<float>();
 }
 
 int64_t bn_workspace_floats(int64_t M, int64_t C, int64_t elem_bytes) {
@@ -491,9 +571,9 @@ int64_t bn_mask_bytes(int64_t M, int64_t C, int64_t elem_bytes) {
 
 // per-layer in-launch finalize state (bn_act.hip FinSync): a zero-initialised
 // uint8 GPU tensor of at least bn_fin_state_bytes(C), kept by the layer
-void* fin_state(const c10::optional<at::Tensor>& fin, int64_t C) {
-  if (!fin.has_value() || !fin->defined()) return nullptr;
-  TORCH_CHECK(fin->is_cuda() && fin->is_contiguous() && fin->nbytes() >= gk::bn_fin_state_bytes((int)C) &&
+void* fin_state(const OptTensor& fin, int C) {
+  if (!has(fin)) return nullptr;
+  TORCH_CHECK(fin->is_cuda() && fin->is_contiguous() && fin->nbytes() >= gk::bn_fin_state_bytes(C) &&
                   reinterpret_cast<uintptr_t>(fin->data_ptr()) % 16 == 0,
               "fin: a contiguous, 16-byte aligned GPU tensor of bn_fin_state_bytes(C) bytes");
   return fin->data_ptr();
@@ -501,288 +581,155 @@ void* fin_state(const c10::optional<at::Tensor>& fin, int64_t C) {
 
 int64_t bn_fin_state_bytes(int64_t C) { return (int64_t)gk::bn_fin_state_bytes((int)C); }
 
-void bn_act_forward(at::Tensor x, c10::optional<at::Tensor> res, at::Tensor y, c10::optional<at::Tensor> mask,
-                    c10::optional<at::Tensor> w,
-                    c10::optional<at::Tensor> b, c10::optional<at::Tensor> run_mean,
-                    c10::optional<at::Tensor> run_var, at::Tensor save_mean, at::Tensor save_invstd,
+// pre / pre_rows: statistics pre-reduced by the producer (conv epilogue)
+void bn_act_forward(at::Tensor x, OptTensor res, at::Tensor y, OptTensor mask, OptTensor w, OptTensor b,
+                    OptTensor run_mean, OptTensor run_var, at::Tensor save_mean, at::Tensor save_invstd,
                     at::Tensor scale, at::Tensor shift, at::Tensor ws, double eps, double momentum, bool relu,
-                    c10::optional<at::Tensor> nbt, c10::optional<at::Tensor> pre, int64_t pre_rows,
-                    c10::optional<at::Tensor> fin, c10::optional<at::Tensor> rscale,
-                    c10::optional<at::Tensor> rshift) {
-  check_cl(x, "x");
-  check_cl(y, "y");
-  const int64_t C = channels_of(x);
-  void* fs = fin_state(fin, C);
-  const int64_t M = x.numel() / C;
-  const int eb = x.element_size();
-  TORCH_CHECK(gk::bn_supported((int)C, eb), "channel count not supported by the fused kernel");
-  TORCH_CHECK(y.scalar_type() == x.scalar_type() && y.numel() == x.numel(), "y must match x");
-  const void* rp = nullptr;
-  if (res.has_value() && res->defined()) {
-    check_cl(*res, "residual");
-    TORCH_CHECK(res->scalar_type() == x.scalar_type() && res->numel() == x.numel(), "residual must match x");
-    rp = res->data_ptr();
-  }
+                    OptTensor nbt, OptTensor pre, int64_t pre_rows, OptTensor fin, OptTensor rscale,
+                    OptTensor rshift) {
+  const gk::BnShape sh = bn_shape(x);
+  check_same(x, {&y}, "y");
+  gk::BnResidual r{opt_same(x, res, "residual"), nullptr, nullptr};
   // deferred residual BN: res * rscale + rshift (ops/bn.py _BNDeferFn)
-  const float* rsc = opt_f32(rscale);
-  const float* rsh = opt_f32(rshift);
-  TORCH_CHECK((rsc == nullptr) == (rsh == nullptr), "rscale and rshift go together");
-  if (rsc) {
-    TORCH_CHECK(rp != nullptr, "rscale / rshift need a residual");
-    for (const at::Tensor* t : {&*rscale, &*rshift})
-      TORCH_CHECK(t->scalar_type() == at::kFloat && t->numel() >= C && t->is_cuda() && t->is_contiguous(),
-                  "rscale / rshift: fp32[C]");
+  TORCH_CHECK(has(rscale) == has(rshift), "rscale and rshift go together");
+  if (has(rscale)) {
+    TORCH_CHECK(r.res != nullptr, "rscale / rshift need a residual");
+    r.rscale = opt_channel_buf(rscale, sh.C, "rscale");
+    r.rshift = opt_channel_buf(rshift, sh.C, "rshift");
   }
-  for (const at::Tensor* t : {&save_mean, &save_invstd, &scale, &shift})
-    TORCH_CHECK(t->scalar_type() == at::kFloat && t->numel() >= C && t->is_cuda(), "stat buffers: fp32[C]");
-  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.numel() >= (int64_t)gk::bn_workspace_floats(M, (int)C, eb),
-              "workspace too small");
-  uint8_t* mp = nullptr;
-  if (relu) {
-    TORCH_CHECK(mask.has_value() && mask->defined() && mask->scalar_type() == at::kByte && mask->is_cuda() &&
-                    mask->numel() >= (int64_t)gk::bn_mask_bytes(M, (int)C, eb),
-                "relu needs a uint8 mask of bn_mask_bytes");
-    mp = mask->data_ptr<uint8_t>();
-  }
+  const gk::BnFwdStats st =
+      fwd_stats(w, b, run_mean, run_var, save_mean, save_invstd, scale, shift, eps, momentum, nbt, sh.C);
+  float* wp = check_ws(ws, sh);
+  uint8_t* mp = relu_mask(mask, relu, sh);
+  const gk::BnPartials p = partials(pre, pre_rows, sh.C, "pre");
+  void* fs = fin_state(fin, sh.C);
   c10::DeviceGuard guard(x.device());
-  if (pre.has_value() && pre->defined()) {   // statistics pre-reduced by the producer (conv epilogue)
-    TORCH_CHECK(pre->is_cuda() && pre->scalar_type() == at::kFloat && pre->is_contiguous() && pre->dim() == 3 &&
-                    pre->size(0) == 2 && pre->size(2) == C && pre_rows > 0 && pre_rows <= pre->size(1),
-                "pre must be fp32 [2, rows, C] partials with 0 < pre_rows <= rows");
-    // the finalize reads rows [0, pre_rows) of each half
-    const float* ps = pre->data_ptr<float>();
-    gk::bn_act_forward_pre(x.data_ptr(), rp, y.data_ptr(), mp, M, (int)C, eb, ps, ps + pre->size(1) * C,
-                           (int)pre_rows, opt_f32(w), opt_f32(b), (float)eps, (float)momentum, opt_f32_mut(run_mean),
-                           opt_f32_mut(run_var), save_mean.data_ptr<float>(), save_invstd.data_ptr<float>(),
-                           scale.data_ptr<float>(), shift.data_ptr<float>(), relu ? 1 : 0, opt_i64(nbt),
-                           cur_stream(x), fs, rsc, rsh);
-    return;
-  }
-  gk::bn_act_forward(x.data_ptr(), rp, y.data_ptr(), mp, M, (int)C, eb, opt_f32(w), opt_f32(b), (float)eps,
-                     (float)momentum, opt_f32_mut(run_mean), opt_f32_mut(run_var), save_mean.data_ptr<float>(),
-                     save_invstd.data_ptr<float>(), scale.data_ptr<float>(), shift.data_ptr<float>(),
-                     ws.data_ptr<float>(), relu ? 1 : 0, opt_i64(nbt), cur_stream(x), fs, rsc, rsh);
+  gk::bn_act_forward(sh, x.data_ptr(), r, y.data_ptr(), mp, st, p, wp, relu ? 1 : 0, fs, cur_stream(x));
 }
 
 // statistics + finalize of a BN whose apply is deferred into its consumer
-void bn_act_finalize(at::Tensor x, c10::optional<at::Tensor> w, c10::optional<at::Tensor> b,
-                     c10::optional<at::Tensor> run_mean, c10::optional<at::Tensor> run_var, at::Tensor save_mean,
-                     at::Tensor save_invstd, at::Tensor scale, at::Tensor shift, at::Tensor ws, double eps,
-                     double momentum, c10::optional<at::Tensor> nbt, c10::optional<at::Tensor> pre, int64_t pre_rows) {
-  check_cl(x, "x");
-  const int64_t C = channels_of(x);
-  const int64_t M = x.numel() / C;
-  const int eb = x.element_size();
-  TORCH_CHECK(gk::bn_supported((int)C, eb), "channel count not supported by the fused kernel");
-  for (const at::Tensor* t : {&save_mean, &save_invstd, &scale, &shift})
-    TORCH_CHECK(t->scalar_type() == at::kFloat && t->numel() >= C && t->is_cuda(), "stat buffers: fp32[C]");
-  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.numel() >= (int64_t)gk::bn_workspace_floats(M, (int)C, eb),
-              "workspace too small");
-  const float* ps = nullptr;
-  const float* pq = nullptr;
-  if (pre.has_value() && pre->defined()) {
-    TORCH_CHECK(pre->is_cuda() && pre->scalar_type() == at::kFloat && pre->is_contiguous() && pre->dim() == 3 &&
-                    pre->size(0) == 2 && pre->size(2) == C && pre_rows > 0 && pre_rows <= pre->size(1),
-                "pre must be fp32 [2, rows, C] partials with 0 < pre_rows <= rows");
-    ps = pre->data_ptr<float>();
-    pq = ps + pre->size(1) * C;
-  }
+void bn_act_finalize(at::Tensor x, OptTensor w, OptTensor b, OptTensor run_mean, OptTensor run_var,
+                     at::Tensor save_mean, at::Tensor save_invstd, at::Tensor scale, at::Tensor shift, at::Tensor ws,
+                     double eps, double momentum, OptTensor nbt, OptTensor pre, int64_t pre_rows) {
+  const gk::BnShape sh = bn_shape(x);
+  const gk::BnFwdStats st =
+      fwd_stats(w, b, run_mean, run_var, save_mean, save_invstd, scale, shift, eps, momentum, nbt, sh.C);
+  float* wp = check_ws(ws, sh);
+  const gk::BnPartials p = partials(pre, pre_rows, sh.C, "pre");
   c10::DeviceGuard guard(x.device());
-  gk::bn_act_finalize(x.data_ptr(), M, (int)C, eb, ps, pq, (int)pre_rows, opt_f32(w), opt_f32(b), (float)eps,
-                      (float)momentum, opt_f32_mut(run_mean), opt_f32_mut(run_var), save_mean.data_ptr<float>(),
-                      save_invstd.data_ptr<float>(), scale.data_ptr<float>(), shift.data_ptr<float>(),
-                      ws.data_ptr<float>(), opt_i64(nbt), cur_stream(x));
+  gk::bn_act_finalize(sh, x.data_ptr(), st, p, wp, cur_stream(x));
 }
 
-void bn_act_backward(at::Tensor dy, c10::optional<at::Tensor> mask, at::Tensor x, at::Tensor dx,
-                     c10::optional<at::Tensor> dres, c10::optional<at::Tensor> w, at::Tensor mean, at::Tensor invstd,
-                     at::Tensor dgamma, at::Tensor dbeta, at::Tensor ws, bool relu,
-                     c10::optional<at::Tensor> gw_acc, c10::optional<at::Tensor> gb_acc,
-                     c10::optional<at::Tensor> dy2, c10::optional<at::Tensor> fin) {
-  check_cl(dy, "dy");
-  check_cl(x, "x");
-  check_cl(dx, "dx");
-  const int64_t C = channels_of(x);
-  void* fs = fin_state(fin, C);
-  const int64_t M = x.numel() / C;
-  const int eb = x.element_size();
-  TORCH_CHECK(dy.scalar_type() == x.scalar_type() && dx.scalar_type() == x.scalar_type(), "dtype mismatch");
-  const uint8_t* mp = nullptr;
-  if (relu) {
-    TORCH_CHECK(mask.has_value() && mask->defined() && mask->scalar_type() == at::kByte &&
-                    mask->numel() >= (int64_t)gk::bn_mask_bytes(M, (int)C, eb),
-                "relu backward needs the forward's mask");
-    mp = mask->data_ptr<uint8_t>();
-  }
-  void* rp = nullptr;
-  if (dres.has_value() && dres->defined()) {
-    check_cl(*dres, "dres");
-    rp = dres->data_ptr();
-  }
-  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.numel() >= (int64_t)gk::bn_workspace_floats(M, (int)C, eb),
-              "workspace too small");
+void bn_act_backward(at::Tensor dy, OptTensor mask, at::Tensor x, at::Tensor dx, OptTensor dres, OptTensor w,
+                     at::Tensor mean, at::Tensor invstd, at::Tensor dgamma, at::Tensor dbeta, at::Tensor ws, bool relu,
+                     OptTensor gw_acc, OptTensor gb_acc, OptTensor dy2, OptTensor fin) {
+  const gk::BnShape sh = bn_shape(x);
+  check_same(x, {&dy}, "dy");
+  check_same(x, {&dx}, "dx");
+  void* rp = opt_same(x, dres, "dres");
+  const void* d2 = opt_dy2(dy2, dy);
+  const gk::BnBwdStats bs = bwd_stats(w, mean, invstd, dgamma, dbeta, gw_acc, gb_acc, sh.C);
+  float* wp = check_ws(ws, sh);
+  const uint8_t* mp = relu_mask(mask, relu, sh);
+  void* fs = fin_state(fin, sh.C);
   c10::DeviceGuard guard(x.device());
-  const void* d2 = opt_like(dy2, dy, "dy2");
-  gk::bn_act_backward(dy.data_ptr(), d2, mp, x.data_ptr(), dx.data_ptr(), rp, M, (int)C, eb, opt_f32(w),
-                      mean.data_ptr<float>(), invstd.data_ptr<float>(), dgamma.data_ptr<float>(),
-                      dbeta.data_ptr<float>(), ws.data_ptr<float>(), relu ? 1 : 0, opt_f32_mut(gw_acc),
-                      opt_f32_mut(gb_acc), cur_stream(x), fs);
+  gk::bn_act_backward(sh, dy.data_ptr(), d2, mp, x.data_ptr(), dx.data_ptr(), rp, bs, wp, relu ? 1 : 0, fs,
+                      cur_stream(x));
 }
 
-void bn_act_backward_pre(at::Tensor dz, at::Tensor x, at::Tensor dx, c10::optional<at::Tensor> w, at::Tensor mean,
-                         at::Tensor invstd, at::Tensor dgamma, at::Tensor dbeta, at::Tensor part, int64_t rows,
-                         c10::optional<at::Tensor> gw_acc, c10::optional<at::Tensor> gb_acc,
-                         c10::optional<at::Tensor> fin) {
-  check_cl(dz, "dz");
-  check_cl(x, "x");
-  check_cl(dx, "dx");
-  const int64_t C = channels_of(x);
-  void* fs = fin_state(fin, C);
-  const int64_t M = x.numel() / C;
-  TORCH_CHECK((x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kFloat) &&
-                  dz.scalar_type() == x.scalar_type() && dx.scalar_type() == x.scalar_type() &&
-                  dz.numel() == x.numel() && dx.numel() == x.numel(),
-              "bn_act_backward_pre: dz / x / dx of one shape and dtype (bf16 or fp32)");
-  const int eb = (int)x.element_size();
-  TORCH_CHECK(gk::bn_supported((int)C, eb), "channel count not supported by the fused kernel");
-  TORCH_CHECK(part.is_cuda() && part.scalar_type() == at::kFloat && part.is_contiguous() && part.dim() == 3 &&
-                  part.size(0) == 2 && part.size(2) == C && rows > 0 && rows <= part.size(1),
-              "part must be fp32 [2, rows, C] partials with 0 < rows <= part.size(1)");
-  for (const at::Tensor* t : {&mean, &invstd, &dgamma, &dbeta})
-    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->numel() >= C, "per-channel buffers: fp32[C]");
+void bn_act_backward_pre(at::Tensor dz, at::Tensor x, at::Tensor dx, OptTensor w, at::Tensor mean, at::Tensor invstd,
+                         at::Tensor dgamma, at::Tensor dbeta, at::Tensor part, int64_t rows, OptTensor gw_acc,
+                         OptTensor gb_acc, OptTensor fin) {
+  const gk::BnShape sh = bn_shape(x);
+  check_same(x, {&dz}, "dz");
+  check_same(x, {&dx}, "dx");
+  const gk::BnBwdStats bs = bwd_stats(w, mean, invstd, dgamma, dbeta, gw_acc, gb_acc, sh.C);
+  const gk::BnPartials p = partials(part, rows, sh.C, "part");
+  void* fs = fin_state(fin, sh.C);
   c10::DeviceGuard guard(x.device());
-  const float* ps = part.data_ptr<float>();
-  gk::bn_act_backward_pre(dz.data_ptr(), x.data_ptr(), dx.data_ptr(), M, (int)C, eb, opt_f32(w), mean.data_ptr<float>(),
-                          invstd.data_ptr<float>(), dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), ps,
-                          ps + part.size(1) * C, (int)rows, opt_f32_mut(gw_acc), opt_f32_mut(gb_acc), cur_stream(x),
-                          fs);
+  gk::bn_act_backward_pre(sh, dz.data_ptr(), x.data_ptr(), dx.data_ptr(), bs, p, fs, cur_stream(x));
 }
 
 // bn_act_backward_pre + the deferred residual BN of x2 (dx2 from the same apply pass)
-void bn_act_backward_pre_dual(at::Tensor dz, at::Tensor x, at::Tensor dx, c10::optional<at::Tensor> w, at::Tensor mean,
+void bn_act_backward_pre_dual(at::Tensor dz, at::Tensor x, at::Tensor dx, OptTensor w, at::Tensor mean,
                               at::Tensor invstd, at::Tensor dgamma, at::Tensor dbeta, at::Tensor part, int64_t rows,
-                              c10::optional<at::Tensor> gw_acc, c10::optional<at::Tensor> gb_acc, at::Tensor x2,
-                              at::Tensor dx2, c10::optional<at::Tensor> w2, at::Tensor mean2, at::Tensor invstd2,
-                              at::Tensor dgamma2, at::Tensor dbeta2, at::Tensor ws2,
-                              c10::optional<at::Tensor> gw2_acc, c10::optional<at::Tensor> gb2_acc) {
-  for (const at::Tensor* t : {&dz, &x, &dx, &x2, &dx2}) check_cl(*t, "dz / x / dx / x2 / dx2");
-  const int64_t C = channels_of(x);
-  const int64_t M = x.numel() / C;
-  for (const at::Tensor* t : {&dz, &dx, &x2, &dx2})
-    TORCH_CHECK(t->scalar_type() == x.scalar_type() && t->numel() == x.numel(),
-                "bn_act_backward_pre_dual: dz / x / dx / x2 / dx2 of one shape and dtype");
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kFloat, "bf16 or fp32");
-  const int eb = (int)x.element_size();
-  TORCH_CHECK(gk::bn_supported((int)C, eb), "channel count not supported by the fused kernel");
-  TORCH_CHECK(part.is_cuda() && part.scalar_type() == at::kFloat && part.is_contiguous() && part.dim() == 3 &&
-                  part.size(0) == 2 && part.size(2) == C && rows > 0 && rows <= part.size(1),
-              "part must be fp32 [2, rows, C] partials with 0 < rows <= part.size(1)");
-  for (const at::Tensor* t : {&mean, &invstd, &dgamma, &dbeta, &mean2, &invstd2, &dgamma2, &dbeta2})
-    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->numel() >= C, "per-channel buffers: fp32[C]");
-  TORCH_CHECK(ws2.scalar_type() == at::kFloat && ws2.numel() >= (int64_t)gk::bn_workspace_floats(M, (int)C, eb),
-              "workspace too small");
+                              OptTensor gw_acc, OptTensor gb_acc, at::Tensor x2, at::Tensor dx2, OptTensor w2,
+                              at::Tensor mean2, at::Tensor invstd2, at::Tensor dgamma2, at::Tensor dbeta2,
+                              at::Tensor ws2, OptTensor gw2_acc, OptTensor gb2_acc) {
+  const gk::BnShape sh = bn_shape(x);
+  check_same(x, {&dz, &dx, &x2, &dx2}, "dz / dx / x2 / dx2");
+  const gk::BnBwdStats bs = bwd_stats(w, mean, invstd, dgamma, dbeta, gw_acc, gb_acc, sh.C);
+  const gk::BnBwdStats bs2 = bwd_stats(w2, mean2, invstd2, dgamma2, dbeta2, gw2_acc, gb2_acc, sh.C);
+  const gk::BnPartials p = partials(part, rows, sh.C, "part");
+  float* wp2 = check_ws(ws2, sh);
   c10::DeviceGuard guard(x.device());
-  const float* ps = part.data_ptr<float>();
-  gk::bn_act_backward_pre_dual(dz.data_ptr(), x.data_ptr(), dx.data_ptr(), M, (int)C, eb, opt_f32(w),
-                               mean.data_ptr<float>(), invstd.data_ptr<float>(), dgamma.data_ptr<float>(),
-                               dbeta.data_ptr<float>(), ps, ps + part.size(1) * C, (int)rows, opt_f32_mut(gw_acc),
-                               opt_f32_mut(gb_acc), x2.data_ptr(), dx2.data_ptr(), opt_f32(w2), mean2.data_ptr<float>(),
-                               invstd2.data_ptr<float>(), dgamma2.data_ptr<float>(), dbeta2.data_ptr<float>(),
-                               ws2.data_ptr<float>(), opt_f32_mut(gw2_acc), opt_f32_mut(gb2_acc), cur_stream(x));
+  gk::bn_act_backward_pre_dual(sh, dz.data_ptr(), x.data_ptr(), dx.data_ptr(), bs, p, x2.data_ptr(), dx2.data_ptr(),
+                               bs2, wp2, cur_stream(x));
 }
 
 // ---- lazy BN backward (bn_act.hip bn_bwd_finalize_lazy): no apply pass ----
-void check_lazy_out(const at::Tensor& x, int64_t C, const at::Tensor& coef, const at::Tensor& padz,
-                    const at::Tensor& padx) {
+gk::BnLazyOut lazy_out(const at::Tensor& x, int C, const at::Tensor& coef, const at::Tensor& padz,
+                       const at::Tensor& padx) {
   TORCH_CHECK(coef.is_cuda() && coef.scalar_type() == at::kFloat && coef.is_contiguous() && coef.numel() >= 4 * C,
               "coef must be a contiguous fp32 [C, 4] GPU tensor");
   for (const at::Tensor* t : {&padz, &padx})
     TORCH_CHECK(t->is_cuda() && t->scalar_type() == x.scalar_type() && t->is_contiguous() && t->numel() >= C,
                 "padz / padx must be contiguous [C] GPU tensors of x's dtype");
+  return {coef.data_ptr<float>(), padz.data_ptr(), padx.data_ptr()};
 }
 
-void bn_bwd_lazy_pre(at::Tensor x, at::Tensor part, int64_t rows, c10::optional<at::Tensor> w, at::Tensor mean,
-                     at::Tensor invstd, at::Tensor dgamma, at::Tensor dbeta, at::Tensor coef, at::Tensor padz,
-                     at::Tensor padx, c10::optional<at::Tensor> gw_acc, c10::optional<at::Tensor> gb_acc) {
-  check_cl(x, "x");
-  const int64_t C = channels_of(x);
-  const int64_t M = x.numel() / C;
-  TORCH_CHECK(part.is_cuda() && part.scalar_type() == at::kFloat && part.is_contiguous() && part.dim() == 3 &&
-                  part.size(0) == 2 && part.size(2) == C && rows > 0 && rows <= part.size(1),
-              "part must be fp32 [2, rows, C] partials with 0 < rows <= part.size(1)");
-  for (const at::Tensor* t : {&mean, &invstd, &dgamma, &dbeta})
-    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->numel() >= C, "per-channel buffers: fp32[C]");
-  check_lazy_out(x, C, coef, padz, padx);
+void bn_bwd_lazy_pre(at::Tensor x, at::Tensor part, int64_t rows, OptTensor w, at::Tensor mean, at::Tensor invstd,
+                     at::Tensor dgamma, at::Tensor dbeta, at::Tensor coef, at::Tensor padz, at::Tensor padx,
+                     OptTensor gw_acc, OptTensor gb_acc) {
+  const gk::BnShape sh = bn_shape(x);
+  const gk::BnPartials p = partials(part, rows, sh.C, "part");
+  const gk::BnBwdStats bs = bwd_stats(w, mean, invstd, dgamma, dbeta, gw_acc, gb_acc, sh.C);
+  const gk::BnLazyOut lz = lazy_out(x, sh.C, coef, padz, padx);
   c10::DeviceGuard guard(x.device());
-  const float* ps = part.data_ptr<float>();
-  gk::bn_bwd_finalize_lazy(ps, ps + part.size(1) * C, (int)rows, M, (int)C, (int)x.element_size(), 1, opt_f32(w),
-                           mean.data_ptr<float>(), invstd.data_ptr<float>(), dgamma.data_ptr<float>(),
-                           dbeta.data_ptr<float>(), opt_f32_mut(gw_acc), opt_f32_mut(gb_acc), coef.data_ptr<float>(),
-                           padz.data_ptr(), padx.data_ptr(), cur_stream(x));
+  gk::bn_bwd_finalize_lazy(sh, p, 1, bs, lz, cur_stream(x));
 }
 
-void bn_act_backward_lazy(at::Tensor dy, c10::optional<at::Tensor> dy2, c10::optional<at::Tensor> mask, at::Tensor x,
-                          at::Tensor dz, c10::optional<at::Tensor> w, at::Tensor mean, at::Tensor invstd,
-                          at::Tensor dgamma, at::Tensor dbeta, at::Tensor ws, bool relu, at::Tensor coef,
-                          at::Tensor padz, at::Tensor padx, c10::optional<at::Tensor> gw_acc,
-                          c10::optional<at::Tensor> gb_acc) {
-  check_cl(dy, "dy");
-  check_cl(x, "x");
-  check_cl(dz, "dz");
-  const int64_t C = channels_of(x);
-  const int64_t M = x.numel() / C;
-  const int eb = x.element_size();
-  TORCH_CHECK(dy.scalar_type() == x.scalar_type() && dz.scalar_type() == x.scalar_type() && dz.numel() == x.numel(),
-              "dtype / shape mismatch");
-  TORCH_CHECK(gk::bn_supported((int)C, eb), "channel count not supported by the fused kernel");
-  const uint8_t* mp = nullptr;
-  if (relu) {
-    TORCH_CHECK(mask.has_value() && mask->defined() && mask->scalar_type() == at::kByte &&
-                    mask->numel() >= (int64_t)gk::bn_mask_bytes(M, (int)C, eb),
-                "relu backward needs the forward's mask");
-    mp = mask->data_ptr<uint8_t>();
-  }
-  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.numel() >= (int64_t)gk::bn_workspace_floats(M, (int)C, eb),
-              "workspace too small");
-  check_lazy_out(x, C, coef, padz, padx);
+void bn_act_backward_lazy(at::Tensor dy, OptTensor dy2, OptTensor mask, at::Tensor x, at::Tensor dz, OptTensor w,
+                          at::Tensor mean, at::Tensor invstd, at::Tensor dgamma, at::Tensor dbeta, at::Tensor ws,
+                          bool relu, at::Tensor coef, at::Tensor padz, at::Tensor padx, OptTensor gw_acc,
+                          OptTensor gb_acc) {
+  const gk::BnShape sh = bn_shape(x);
+  check_same(x, {&dy}, "dy");
+  check_same(x, {&dz}, "dz");
+  const void* d2 = opt_dy2(dy2, dy);
+  const gk::BnBwdStats bs = bwd_stats(w, mean, invstd, dgamma, dbeta, gw_acc, gb_acc, sh.C);
+  float* wp = check_ws(ws, sh);
+  const uint8_t* mp = relu_mask(mask, relu, sh);
+  const gk::BnLazyOut lz = lazy_out(x, sh.C, coef, padz, padx);
   c10::DeviceGuard guard(x.device());
-  const void* d2 = opt_like(dy2, dy, "dy2");
-  gk::bn_act_backward_lazy(dy.data_ptr(), d2, mp, x.data_ptr(), dz.data_ptr(), M, (int)C, eb, opt_f32(w),
-                           mean.data_ptr<float>(), invstd.data_ptr<float>(), dgamma.data_ptr<float>(),
-                           dbeta.data_ptr<float>(), ws.data_ptr<float>(), relu ? 1 : 0, opt_f32_mut(gw_acc),
-                           opt_f32_mut(gb_acc), coef.data_ptr<float>(), padz.data_ptr(), padx.data_ptr(),
+  gk::bn_act_backward_lazy(sh, dy.data_ptr(), d2, mp, x.data_ptr(), dz.data_ptr(), bs, wp, relu ? 1 : 0, lz,
                            cur_stream(x));
 }
 
 void bn_stats_partials(at::Tensor x, at::Tensor ws) {
-  check_cl(x, "x");
-  const int64_t C = channels_of(x);
-  const int64_t M = x.numel() / C;
-  const int eb = (int)x.element_size();
-  TORCH_CHECK(gk::bn_supported((int)C, eb), "channel count not supported by the fused kernel");
-  TORCH_CHECK(ws.is_cuda() && ws.scalar_type() == at::kFloat && ws.numel() >= (int64_t)gk::bn_workspace_floats(M, (int)C, eb),
-              "workspace too small");
+  const gk::BnShape sh = bn_shape(x);
+  float* wp = check_ws(ws, sh);
   c10::DeviceGuard guard(x.device());
-  gk::bn_stats_partials(x.data_ptr(), M, (int)C, eb, ws.data_ptr<float>(), cur_stream(x));
+  gk::bn_stats_partials(sh, x.data_ptr(), wp, cur_stream(x));
 }
 
 void bn_lazy_apply(at::Tensor dz, at::Tensor x, at::Tensor dx, at::Tensor coef) {
-  check_cl(dz, "dz");
-  check_cl(x, "x");
-  check_cl(dx, "dx");
-  const int64_t C = channels_of(x);
-  const int64_t M = x.numel() / C;
-  TORCH_CHECK(dz.scalar_type() == x.scalar_type() && dx.scalar_type() == x.scalar_type() &&
-                  dz.numel() == x.numel() && dx.numel() == x.numel(), "dz / x / dx of one shape and dtype");
-  TORCH_CHECK(gk::bn_supported((int)C, (int)x.element_size()), "channel count not supported by the fused kernel");
-  TORCH_CHECK(coef.is_cuda() && coef.scalar_type() == at::kFloat && coef.numel() >= 4 * C, "coef: fp32 [C, 4]");
+  const gk::BnShape sh = bn_shape(x);
+  check_same(x, {&dz}, "dz");
+  check_same(x, {&dx}, "dx");
+  TORCH_CHECK(coef.is_cuda() && coef.scalar_type() == at::kFloat && coef.is_contiguous() && coef.numel() >= 4 * sh.C,
+              "coef must be a contiguous fp32 [C, 4] GPU tensor");
   c10::DeviceGuard guard(x.device());
-  gk::bn_lazy_apply(dz.data_ptr(), x.data_ptr(), dx.data_ptr(), M, (int)C, (int)x.element_size(),
-                    coef.data_ptr<float>(), cur_stream(x));
+  gk::bn_lazy_apply(sh, dz.data_ptr(), x.data_ptr(), dx.data_ptr(), coef.data_ptr<float>(), cur_stream(x));
 }
 
-gk::PoolGeo pool_geo(const at::Tensor& x, const at::Tensor& y, int64_t k, int64_t st, int64_t pad) {
-  TORCH_CHECK(x.dim() == 4 && y.dim() == 4 && x.size(0) == y.size(0) && x.size(1) == y.size(1), "pool shapes");
+// x: the pool's input, y: a tensor of the pool's output shape and x's dtype
+gk::PoolGeo pool_geo(const at::Tensor& x, const at::Tensor& y, const char* y_name, int64_t k, int64_t st,
+                     int64_t pad) {
+  check_cl(y, y_name);
+  TORCH_CHECK(x.dim() == 4 && y.dim() == 4 && x.size(0) == y.size(0) && x.size(1) == y.size(1) &&
+                  y.scalar_type() == x.scalar_type(),
+              y_name, " must be 4-D with x's batch, channels and dtype");
   gk::PoolGeo pg;
   pg.H = (int)x.size(2);
   pg.W = (int)x.size(3);
@@ -798,67 +745,40 @@ gk::PoolGeo pool_geo(const at::Tensor& x, const at::Tensor& y, int64_t k, int64_
   return pg;
 }
 
-void bn_relu_pool_forward(at::Tensor x, at::Tensor y, at::Tensor amax, c10::optional<at::Tensor> w,
-                          c10::optional<at::Tensor> b, c10::optional<at::Tensor> run_mean,
-                          c10::optional<at::Tensor> run_var, at::Tensor save_mean, at::Tensor save_invstd,
-                          at::Tensor scale, at::Tensor shift, at::Tensor ws, double eps, double momentum, int64_t k,
-                          int64_t st, int64_t pad, c10::optional<at::Tensor> nbt, c10::optional<at::Tensor> pre,
-                          int64_t pre_rows) {
-  check_cl(x, "x");
-  check_cl(y, "y");
-  TORCH_CHECK(x.dim() == 4 && y.scalar_type() == x.scalar_type(), "y must be 4-D with x's dtype");
-  const gk::PoolGeo pg = pool_geo(x, y, k, st, pad);
-  const int64_t C = x.size(1);
-  const int64_t M = x.numel() / C;
-  const int eb = x.element_size();
-  TORCH_CHECK(gk::bn_supported((int)C, eb), "channel count not supported by the fused kernel");
-  TORCH_CHECK(amax.scalar_type() == at::kByte && amax.is_cuda() && amax.numel() >= y.numel(), "amax: uint8[y.numel]");
-  for (const at::Tensor* t : {&save_mean, &save_invstd, &scale, &shift})
-    TORCH_CHECK(t->scalar_type() == at::kFloat && t->numel() >= C && t->is_cuda(), "stat buffers: fp32[C]");
-  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.numel() >= (int64_t)gk::bn_workspace_floats(M, (int)C, eb),
-              "workspace too small");
-  c10::DeviceGuard guard(x.device());
-  if (pre.has_value() && pre->defined()) {   // statistics pre-reduced by the producer (stem conv epilogue)
-    TORCH_CHECK(pre->is_cuda() && pre->scalar_type() == at::kFloat && pre->is_contiguous() && pre->dim() == 3 &&
-                    pre->size(0) == 2 && pre->size(2) == C && pre_rows > 0 && pre_rows <= pre->size(1),
-                "pre must be fp32 [2, rows, C] partials with 0 < pre_rows <= rows");
-    const float* ps = pre->data_ptr<float>();
-    gk::bn_relu_pool_forward_pre(x.data_ptr(), y.data_ptr(), amax.data_ptr<uint8_t>(), x.size(0), (int)C, pg, eb, ps,
-                                 ps + pre->size(1) * C, (int)pre_rows, opt_f32(w), opt_f32(b), (float)eps,
-                                 (float)momentum, opt_f32_mut(run_mean), opt_f32_mut(run_var),
-                                 save_mean.data_ptr<float>(), save_invstd.data_ptr<float>(), scale.data_ptr<float>(),
-                                 shift.data_ptr<float>(), opt_i64(nbt), cur_stream(x));
-    return;
-  }
-  gk::bn_relu_pool_forward(x.data_ptr(), y.data_ptr(), amax.data_ptr<uint8_t>(), x.size(0), (int)C, pg, eb,
-                           opt_f32(w), opt_f32(b), (float)eps, (float)momentum, opt_f32_mut(run_mean),
-                           opt_f32_mut(run_var), save_mean.data_ptr<float>(), save_invstd.data_ptr<float>(),
-                           scale.data_ptr<float>(), shift.data_ptr<float>(), ws.data_ptr<float>(), opt_i64(nbt),
-                           cur_stream(x));
+uint8_t* pool_amax(const at::Tensor& amax, const at::Tensor& y) {
+  TORCH_CHECK(amax.is_cuda() && amax.scalar_type() == at::kByte && amax.numel() >= y.numel(),
+              "amax: a uint8 GPU tensor of the pooled tensor's element count");
+  return amax.data_ptr<uint8_t>();
 }
 
-void bn_relu_pool_backward(at::Tensor dy, at::Tensor amax, at::Tensor x, at::Tensor dx, c10::optional<at::Tensor> w,
-                           at::Tensor mean, at::Tensor invstd, at::Tensor dgamma, at::Tensor dbeta, at::Tensor ws,
-                           int64_t k, int64_t st, int64_t pad, c10::optional<at::Tensor> gw_acc,
-                           c10::optional<at::Tensor> gb_acc, c10::optional<at::Tensor> dy2) {
-  check_cl(dy, "dy");
-  check_cl(x, "x");
-  check_cl(dx, "dx");
-  TORCH_CHECK(dy.scalar_type() == x.scalar_type() && dx.scalar_type() == x.scalar_type(), "dtype mismatch");
-  TORCH_CHECK(dx.sizes() == x.sizes(), "dx must match x");
-  const gk::PoolGeo pg = pool_geo(x, dy, k, st, pad);
-  const int64_t C = x.size(1);
-  const int64_t M = x.numel() / C;
-  const int eb = x.element_size();
-  TORCH_CHECK(amax.scalar_type() == at::kByte && amax.numel() >= dy.numel(), "amax: uint8[dy.numel]");
-  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.numel() >= (int64_t)gk::bn_workspace_floats(M, (int)C, eb),
-              "workspace too small");
+// pre / pre_rows: statistics pre-reduced by the producer (stem conv epilogue)
+void bn_relu_pool_forward(at::Tensor x, at::Tensor y, at::Tensor amax, OptTensor w, OptTensor b, OptTensor run_mean,
+                          OptTensor run_var, at::Tensor save_mean, at::Tensor save_invstd, at::Tensor scale,
+                          at::Tensor shift, at::Tensor ws, double eps, double momentum, int64_t k, int64_t st,
+                          int64_t pad, OptTensor nbt, OptTensor pre, int64_t pre_rows) {
+  const gk::BnShape sh = bn_shape(x);
+  const gk::PoolGeo pg = pool_geo(x, y, "y", k, st, pad);
+  uint8_t* ap = pool_amax(amax, y);
+  const gk::BnFwdStats fst =
+      fwd_stats(w, b, run_mean, run_var, save_mean, save_invstd, scale, shift, eps, momentum, nbt, sh.C);
+  float* wp = check_ws(ws, sh);
+  const gk::BnPartials p = partials(pre, pre_rows, sh.C, "pre");
   c10::DeviceGuard guard(x.device());
-  const void* d2 = opt_like(dy2, dy, "dy2");
-  gk::bn_relu_pool_backward(dy.data_ptr(), d2, amax.data_ptr<uint8_t>(), x.data_ptr(), dx.data_ptr(), x.size(0), (int)C,
-                            pg, eb, opt_f32(w), mean.data_ptr<float>(), invstd.data_ptr<float>(),
-                            dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), ws.data_ptr<float>(),
-                            opt_f32_mut(gw_acc), opt_f32_mut(gb_acc), cur_stream(x));
+  gk::bn_relu_pool_forward(sh, pg, x.data_ptr(), y.data_ptr(), ap, fst, p, wp, cur_stream(x));
+}
+
+void bn_relu_pool_backward(at::Tensor dy, at::Tensor amax, at::Tensor x, at::Tensor dx, OptTensor w, at::Tensor mean,
+                           at::Tensor invstd, at::Tensor dgamma, at::Tensor dbeta, at::Tensor ws, int64_t k,
+                           int64_t st, int64_t pad, OptTensor gw_acc, OptTensor gb_acc, OptTensor dy2) {
+  const gk::BnShape sh = bn_shape(x);
+  check_same(x, {&dx}, "dx");
+  const gk::PoolGeo pg = pool_geo(x, dy, "dy", k, st, pad);
+  const uint8_t* ap = pool_amax(amax, dy);
+  const void* d2 = opt_dy2(dy2, dy);
+  const gk::BnBwdStats bs = bwd_stats(w, mean, invstd, dgamma, dbeta, gw_acc, gb_acc, sh.C);
+  float* wp = check_ws(ws, sh);
+  c10::DeviceGuard guard(x.device());
+  gk::bn_relu_pool_backward(sh, pg, dy.data_ptr(), d2, ap, x.data_ptr(), dx.data_ptr(), bs, wp, cur_stream(x));
 }
 
 // ---------------------------------------------------------------------------

@@ -454,8 +454,6 @@ __global__ __launch_bounds__(kBlock) void bn_apply_kernel(const T* __restrict__ 
       });
 }
 
-__device__ __forceinline__ float round_bf16(float f) { return __uint_as_float((uint32_t)f32_to_bf16(f) << 16); }
-
 // Fused BN apply + ReLU + max-pool (the ResNet stem): one thread per 16-byte
 // channel vector of one OUTPUT pixel walks its k x k window, normalises each
 // input on the fly and keeps the max of the (dtype-rounded) pre-ReLU values.
@@ -507,7 +505,7 @@ __global__ __launch_bounds__(kBlock) void bn_relu_pool_kernel(const T* __restric
 #pragma unroll
       for (int i = 0; i < V; ++i) {
         float z = fmaf(v[q][i], sc[i], sf[i]);
-        if (sizeof(T) == 2) z = round_bf16(z);
+        if (sizeof(T) == 2) z = round_to_bf16(z);
         if (z > m[i] || z != z) {
           m[i] = z;
           idx[i] = (uint32_t)q;
@@ -527,7 +525,7 @@ __global__ __launch_bounds__(kBlock) void bn_relu_pool_kernel(const T* __restric
 #pragma unroll
         for (int i = 0; i < V; ++i) {
           float z = fmaf(v[i], sc[i], sf[i]);
-          if (sizeof(T) == 2) z = round_bf16(z);
+          if (sizeof(T) == 2) z = round_to_bf16(z);
           if (z > m[i] || z != z) {
             m[i] = z;
             idx[i] = pos;
@@ -1050,7 +1048,6 @@ __global__ __launch_bounds__(kBlock) void bn_pool_tile_kernel(const T* __restric
 constexpr int kPoolTargetBlocks = 4096;
 // blocks per streaming pass (<= kPoolTargetBlocks: the workspace is sized for that)
 int g_bn_blocks = 1024;
-#define kTargetBlocks g_bn_blocks
 
 // In-launch finalize for one launch of grid g, or a FinSync with ticket ==
 // nullptr (separate finalize launch): needs the per-layer state, no stream
@@ -1075,53 +1072,73 @@ FinSync make_fin(void* state, const Geo& g, int C, hipStream_t s) {
   return fs;
 }
 
-}  // namespace
-
-size_t bn_fin_state_bytes(int C) { return kFinStateFlagsOffset + sizeof(uint32_t) * (size_t)((C + kFinC - 1) / kFinC); }
-
-size_t bn_workspace_floats(int64_t M, int C, int elem_bytes) {
-  // sized for the larger (pool-backward) grid so one workspace fits every pass
-  const Geo g =
-      elem_bytes == 2 ? make_geo<uint16_t>(M, C, kPoolTargetBlocks) : make_geo<float>(M, C, kPoolTargetBlocks);
-  return (size_t)2 * g.gy * C;
+// f(T{}) with T the element type of the activations: uint16_t (bf16) or float
+template <class F>
+void with_elem(int elem_bytes, F&& f) {
+  if (elem_bytes == 2) f(uint16_t{});
+  else f(float{});
 }
 
-void bn_set_blocks(int blocks) { g_bn_blocks = blocks < 64 ? 64 : blocks > kPoolTargetBlocks ? kPoolTargetBlocks : blocks; }
+dim3 fin_grid(int C) { return dim3((C + kFinC - 1) / kFinC); }
+dim3 grid_of(const Geo& g) { return dim3(g.gx, g.gy); }
 
-bool bn_supported(int C, int elem_bytes) {
-  const int V = elem_bytes == 2 ? 8 : 4;
-  return C % V == 0 && C >= V;
+// the two [gy][C] halves of a workspace that takes the partials of grid g
+struct WsParts {
+  float* a;
+  float* b;
+  int gy;
+  operator BnPartials() const { return {a, b, gy}; }
+};
+WsParts ws_parts(float* ws, const Geo& g, int C) { return {ws, ws + (int64_t)g.gy * C, g.gy}; }
+
+FwdFin fwd_fin(const BnFwdStats& st, BnPartials p) {
+  return {p.a, p.b, p.gy, st.w, st.b, st.eps, st.momentum, st.run_mean, st.run_var, st.save_mean, st.save_invstd,
+          st.scale, st.shift, st.nbt};
+}
+// centre: the b partials are sum(dz * x) (GEMM epilogue), centred with the mean by the finalize
+BwdFin bwd_fin(const BnBwdStats& bs, BnPartials p, bool centre = false) {
+  return {p.a, p.b, p.gy, bs.dbeta, bs.dgamma, bs.gb_acc, bs.gw_acc, centre ? bs.mean : nullptr,
+          centre ? bs.invstd : nullptr};
+}
+
+void launch_finalize(const FwdFin& f, int64_t M, int C, hipStream_t s) {
+  hipLaunchKernelGGL(bn_finalize_kernel, fin_grid(C), dim3(kBlock), 0, s, f.psum, f.psq, f.gy, M, C, f.w, f.b, f.eps,
+                     f.momentum, f.run_mean, f.run_var, f.save_mean, f.save_invstd, f.scale, f.shift, f.nbt);
+}
+void launch_bwd_finalize(const BwdFin& f, int C, hipStream_t s) {
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, fin_grid(C), dim3(kBlock), 0, s, f.pdb, f.pdg, f.gy, C, f.dbeta, f.dgamma,
+                     f.gb_acc, f.gw_acc, f.cmean, f.cinvstd);
+}
+
+// the statistics partials of x: the producer's (pre), or the stats pass into ws
+template <typename T>
+BnPartials stats_partials(BnShape sh, const T* x, BnPartials pre, float* ws, hipStream_t s) {
+  if (pre.a) return pre;
+  const Geo g = make_geo<T>(sh.M, sh.C, g_bn_blocks);
+  const WsParts p = ws_parts(ws, g, sh.C);
+  hipLaunchKernelGGL(bn_stats_kernel<T>, grid_of(g), dim3(kBlock), 0, s, x, sh.M, sh.C, g, p.a, p.b);
+  return p;
 }
 
 template <typename T>
-void bn_stats_t(const T* x, int64_t M, int C, const float* w, const float* b, float eps, float momentum,
-                float* run_mean, float* run_var, float* save_mean, float* save_invstd, float* scale, float* shift,
-                float* ws, int64_t* nbt, hipStream_t s) {
-  const Geo g = make_geo<T>(M, C, kTargetBlocks);
-  float* psum = ws;
-  float* psq = ws + (int64_t)g.gy * C;
-  hipLaunchKernelGGL(bn_stats_kernel<T>, dim3(g.gx, g.gy), dim3(kBlock), 0, s, x, M, C, g, psum, psq);
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + kFinC - 1) / kFinC), dim3(kBlock), 0, s, psum, psq, g.gy, M, C,
-                     w, b, eps, momentum, run_mean, run_var, save_mean, save_invstd, scale, shift, nbt);
-}
-
-template <typename T>
-void launch_apply(const T* x, const T* res, T* y, uint8_t* mask, int64_t M, int C, const Geo& g, float* scale,
-                  float* shift, int relu, const FinSync& fs, const FwdFin& ff, hipStream_t s,
-                  const float* rscale = nullptr, const float* rshift = nullptr) {
-  if (res && rscale) {
+void launch_apply(const T* x, BnResidual r, T* y, uint8_t* mask, BnShape sh, const Geo& g, int relu, const FinSync& fs,
+                  const FwdFin& ff, hipStream_t s) {
+  const T* res = static_cast<const T*>(r.res);
+  const int64_t M = sh.M;
+  const int C = sh.C;
+  if (res && r.rscale) {
     // deferred residual BN (its scale / shift finalized by an earlier launch)
     if (relu)
-      hipLaunchKernelGGL((bn_apply_kernel<T, true, true, false, kBnUnroll, true>), dim3(g.gx, g.gy), dim3(kBlock), 0, s,
-                         x, res, y, mask, M, C, g, scale, shift, fs, ff, rscale, rshift);
+      hipLaunchKernelGGL((bn_apply_kernel<T, true, true, false, kBnUnroll, true>), grid_of(g), dim3(kBlock), 0, s, x,
+                         res, y, mask, M, C, g, ff.scale, ff.shift, fs, ff, r.rscale, r.rshift);
     else
-      hipLaunchKernelGGL((bn_apply_kernel<T, false, true, false, kBnUnroll, true>), dim3(g.gx, g.gy), dim3(kBlock), 0,
-                         s, x, res, y, mask, M, C, g, scale, shift, fs, ff, rscale, rshift);
+      hipLaunchKernelGGL((bn_apply_kernel<T, false, true, false, kBnUnroll, true>), grid_of(g), dim3(kBlock), 0, s, x,
+                         res, y, mask, M, C, g, ff.scale, ff.shift, fs, ff, r.rscale, r.rshift);
     return;
   }
-#define GK_APPLY(R, D, F)                                                                                           \
-  hipLaunchKernelGGL((bn_apply_kernel<T, R, D, F>), dim3(g.gx, g.gy), dim3(kBlock), 0, s, x, res, y, mask, M, C, g, \
-                     scale, shift, fs, ff, nullptr, nullptr)
+#define GK_APPLY(R, D, F)                                                                                       \
+  hipLaunchKernelGGL((bn_apply_kernel<T, R, D, F>), grid_of(g), dim3(kBlock), 0, s, x, res, y, mask, M, C, g, \
+                     ff.scale, ff.shift, fs, ff, nullptr, nullptr)
 #define GK_APPLY2(R, D) if (fs.ticket) GK_APPLY(R, D, true); else GK_APPLY(R, D, false);
   if (relu && res) { GK_APPLY2(true, true) }
   else if (relu) { GK_APPLY2(true, false) }
@@ -1131,237 +1148,199 @@ void launch_apply(const T* x, const T* res, T* y, uint8_t* mask, int64_t M, int 
 #undef GK_APPLY
 }
 
-template <typename T>
-void bn_forward_t(const T* x, const T* res, T* y, uint8_t* mask, int64_t M, int C, const float* w, const float* b, float eps,
-                  float momentum, float* run_mean, float* run_var, float* save_mean, float* save_invstd,
-                  float* scale, float* shift, float* ws, int relu, int64_t* nbt, void* fin_state, hipStream_t s,
-                  const float* rscale = nullptr, const float* rshift = nullptr) {
-  const Geo g = make_geo<T>(M, C, kTargetBlocks);
-  if (rscale) fin_state = nullptr;   // the deferred-residual apply has no in-launch finalize form
-  const FinSync fs = make_fin(fin_state, g, C, s);
-  const FwdFin ff{ws, ws + (int64_t)g.gy * C, g.gy, w, b, eps, momentum, run_mean, run_var, save_mean, save_invstd,
-                  scale, shift, nbt};
-  if (fs.ticket) {
-    hipLaunchKernelGGL(bn_stats_kernel<T>, dim3(g.gx, g.gy), dim3(kBlock), 0, s, x, M, C, g, ws, ws + (int64_t)g.gy * C);
-  } else {
-    bn_stats_t<T>(x, M, C, w, b, eps, momentum, run_mean, run_var, save_mean, save_invstd, scale, shift, ws, nbt, s);
-  }
-  launch_apply<T>(x, res, y, mask, M, C, g, scale, shift, relu, fs, ff, s, rscale, rshift);
+// f(src) with src the plain gradient source for (relu, dy2 given)
+template <typename T, class F>
+void with_dy(const T* dy, const T* dy2, const uint8_t* mask, int relu, F&& f) {
+  if (relu && dy2) f(DyPlain<T, true, true>{dy, dy2, mask});
+  else if (relu) f(DyPlain<T, true, false>{dy, dy2, mask});
+  else if (dy2) f(DyPlain<T, false, true>{dy, dy2, mask});
+  else f(DyPlain<T, false, false>{dy, dy2, mask});
+}
+
+// the reduce pass; WDZ: it also writes dz (ReLU-masked, twin-summed dy)
+template <typename T, bool WDZ = false, typename Src>
+void launch_reduce(Src src, const T* x, BnShape sh, const Geo& g, const BnBwdStats& bs, WsParts p, hipStream_t s,
+                   T* dz = nullptr) {
+  hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, Src, WDZ>), grid_of(g), dim3(kBlock), 0, s, src, x, sh.M, sh.C, g,
+                     bs.mean, bs.invstd, p.a, p.b, dz);
 }
 
 // finalize (separate launch unless fs carries the in-launch state) + apply
-template <typename T, typename Src, bool DRES>
-void launch_bwd_apply(Src src, const T* x, T* dx, T* dres, int64_t M, int C, const Geo& g, const float* w,
-                      const float* mean, const float* invstd, const BwdFin& bf, const FinSync& fs, hipStream_t s) {
+template <typename T, bool DRES, typename Src>
+void launch_bwd_apply(Src src, const T* x, T* dx, T* dres, BnShape sh, const Geo& g, const BnBwdStats& bs,
+                      const BwdFin& bf, const FinSync& fs, hipStream_t s) {
   if (fs.ticket) {
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<T, Src, DRES, true>), dim3(g.gx, g.gy), dim3(kBlock), 0, s, src, x, dx,
-                       dres, M, C, g, w, mean, invstd, bf.dbeta, bf.dgamma, fs, bf);
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<T, Src, DRES, true>), grid_of(g), dim3(kBlock), 0, s, src, x, dx, dres,
+                       sh.M, sh.C, g, bs.w, bs.mean, bs.invstd, bs.dbeta, bs.dgamma, fs, bf);
     return;
   }
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + kFinC - 1) / kFinC), dim3(kBlock), 0, s, bf.pdb, bf.pdg, bf.gy,
-                     C, bf.dbeta, bf.dgamma, bf.gb_acc, bf.gw_acc, bf.cmean, bf.cinvstd);
-  hipLaunchKernelGGL((bn_bwd_apply_kernel<T, Src, DRES, false>), dim3(g.gx, g.gy), dim3(kBlock), 0, s, src, x, dx,
-                     dres, M, C, g, w, mean, invstd, bf.dbeta, bf.dgamma, FinSync{}, BwdFin{});
+  launch_bwd_finalize(bf, sh.C, s);
+  hipLaunchKernelGGL((bn_bwd_apply_kernel<T, Src, DRES, false>), grid_of(g), dim3(kBlock), 0, s, src, x, dx, dres,
+                     sh.M, sh.C, g, bs.w, bs.mean, bs.invstd, bs.dbeta, bs.dgamma, FinSync{}, BwdFin{});
 }
 
+// reduce + finalize + apply of dz = src
 template <typename T, typename Src>
-void bn_backward_src(Src src, const T* x, T* dx, T* dres, int64_t M, int C, const float* w, const float* mean,
-                     const float* invstd, float* dgamma, float* dbeta, float* ws, float* gw_acc, float* gb_acc,
-                     void* fin_state, hipStream_t s, int target_blocks = kTargetBlocks) {
-  const Geo g = make_geo<T>(M, C, target_blocks);
-  float* pdb = ws;
-  float* pdg = ws + (int64_t)g.gy * C;
-  hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, Src>), dim3(g.gx, g.gy), dim3(kBlock), 0, s, src, x, M, C, g, mean,
-                     invstd, pdb, pdg);
-  const FinSync fs = make_fin(fin_state, g, C, s);
-  const BwdFin bf{pdb, pdg, g.gy, dbeta, dgamma, gb_acc, gw_acc, nullptr, nullptr};
-  if (dres) launch_bwd_apply<T, Src, true>(src, x, dx, dres, M, C, g, w, mean, invstd, bf, fs, s);
-  else launch_bwd_apply<T, Src, false>(src, x, dx, dres, M, C, g, w, mean, invstd, bf, fs, s);
+void bn_backward_src(Src src, const T* x, T* dx, T* dres, BnShape sh, const BnBwdStats& bs, float* ws, void* fin_state,
+                     hipStream_t s, int target_blocks = g_bn_blocks) {
+  const Geo g = make_geo<T>(sh.M, sh.C, target_blocks);
+  const WsParts p = ws_parts(ws, g, sh.C);
+  launch_reduce<T>(src, x, sh, g, bs, p, s);
+  const FinSync fs = make_fin(fin_state, g, sh.C, s);
+  if (dres) launch_bwd_apply<T, true>(src, x, dx, dres, sh, g, bs, bwd_fin(bs, p), fs, s);
+  else launch_bwd_apply<T, false>(src, x, dx, dres, sh, g, bs, bwd_fin(bs, p), fs, s);
+}
+
+// finalize + apply of a dz that needs no gating, from given partials
+template <typename T>
+void bn_backward_dz(const T* dz, const T* x, T* dx, BnShape sh, const Geo& g, const BnBwdStats& bs, const BwdFin& bf,
+                    void* fin_state, hipStream_t s) {
+  const FinSync fs = make_fin(fin_state, g, sh.C, s);
+  launch_bwd_apply<T, false>(DyPlain<T, false, false>{dz, nullptr, nullptr}, x, dx, (T*)nullptr, sh, g, bs, bf, fs, s);
 }
 
 template <typename T>
-void bn_backward_t(const T* dy, const T* dy2, const uint8_t* mask, const T* x, T* dx, T* dres, int64_t M, int C,
-                   const float* w, const float* mean, const float* invstd, float* dgamma, float* dbeta, float* ws,
-                   int relu, float* gw_acc, float* gb_acc, void* fin_state, hipStream_t s) {
-  if (dy2 && dres) {
-    // twin + residual (ResNet block output): the reduce pass writes dz = dres
-    // and the apply pass reads it back (one tensor instead of dy, dy2, mask)
-    const Geo g = make_geo<T>(M, C, kTargetBlocks);
-    float* pdb = ws;
-    float* pdg = ws + (int64_t)g.gy * C;
-#define GK_RED(R)                                                                                                  \
-  hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, DyPlain<T, R, true>, true>), dim3(g.gx, g.gy), dim3(kBlock), 0, s,     \
-                     DyPlain<T, R, true>{dy, dy2, mask}, x, M, C, g, mean, invstd, pdb, pdg, dres)
-    if (relu) GK_RED(true);
-    else GK_RED(false);
-#undef GK_RED
-    const FinSync fs = make_fin(fin_state, g, C, s);
-    const BwdFin bf{pdb, pdg, g.gy, dbeta, dgamma, gb_acc, gw_acc, nullptr, nullptr};
-    launch_bwd_apply<T, DyPlain<T, false, false>, false>(DyPlain<T, false, false>{dres, nullptr, nullptr}, x, dx,
-                                                         (T*)nullptr, M, C, g, w, mean, invstd, bf, fs, s);
+void launch_pool(const T* x, T* y, uint8_t* amax, BnShape sh, PoolGeo pg, const float* scale, const float* shift,
+                 hipStream_t s) {
+  const int64_t P = sh.M / ((int64_t)pg.H * pg.W) * pg.OH * pg.OW;
+  const int64_t threads = P * (sh.C / Vec<T>::N);
+  const dim3 grid((unsigned)((threads + kBlock - 1) / kBlock));
+  if (pg.k == 3 && pg.p == 1)   // all 9 window loads in flight
+    hipLaunchKernelGGL((bn_relu_pool_kernel<T, 3>), grid, dim3(kBlock), 0, s, x, y, amax, P, sh.C, pg, scale, shift);
+  else
+    hipLaunchKernelGGL(bn_relu_pool_kernel<T>, grid, dim3(kBlock), 0, s, x, y, amax, P, sh.C, pg, scale, shift);
+}
+
+template <typename T, bool TWIN>
+void bn_pool_backward_tw(const T* dy, const T* dy2, const uint8_t* amax, const T* x, T* dx, BnShape sh, PoolGeo pg,
+                         const BnBwdStats& bs, float* ws, hipStream_t s) {
+  const int64_t M = sh.M;
+  const int C = sh.C;
+  const int TH = (pg.H + pg.p + pg.s - 1) / pg.s, TW = (pg.W + pg.p + pg.s - 1) / pg.s;
+  const int64_t ntiles = M / ((int64_t)pg.H * pg.W) * TH * TW;
+  // every window reaching tile th has oh in {th-1, th}.  ntiles <= M: the workspace holds the partials of a
+  // grid over M rows (bn_workspace_floats); a 1-pixel-wide plane under a padded pool has more tiles than
+  // pixels and would get more row chunks than that, so it takes the per-pixel gather.
+  if (pg.s == 2 && pg.k <= 4 && ntiles <= M) {
+    // tile-ordered fast path (3x3/s2 stem pool)
+    const Geo g = make_geo<T>(ntiles, C, kPoolTargetBlocks);
+    const WsParts p = ws_parts(ws, g, C);
+    hipLaunchKernelGGL((bn_pool_tile_kernel<T, TWIN, false>), grid_of(g), dim3(kBlock), 0, s, dy, dy2, amax, x,
+                       (T*)nullptr, ntiles, C, pg, TH, TW, g, M, bs.w, bs.mean, bs.invstd, (const float*)nullptr,
+                       (const float*)nullptr, p.a, p.b);
+    launch_bwd_finalize(bwd_fin(bs, p), C, s);
+    hipLaunchKernelGGL((bn_pool_tile_kernel<T, TWIN, true>), grid_of(g), dim3(kBlock), 0, s, dy, dy2, amax, x, dx,
+                       ntiles, C, pg, TH, TW, g, M, bs.w, bs.mean, bs.invstd, bs.dbeta, bs.dgamma, (float*)nullptr,
+                       (float*)nullptr);
     return;
   }
-#define GK_BWD(R, TW)                                                                                              \
-  bn_backward_src<T>(DyPlain<T, R, TW>{dy, dy2, mask}, x, dx, dres, M, C, w, mean, invstd, dgamma, dbeta, ws, gw_acc, \
-                     gb_acc, fin_state, s)
-  if (relu && dy2) GK_BWD(true, true);
-  else if (relu) GK_BWD(true, false);
-  else if (dy2) GK_BWD(false, true);
-  else GK_BWD(false, false);
-#undef GK_BWD
-}
-
-size_t bn_mask_bytes(int64_t M, int C, int elem_bytes) { return (size_t)M * (size_t)(C / (elem_bytes == 2 ? 8 : 4)); }
-
-void bn_stats_partials(const void* x, int64_t M, int C, int elem_bytes, float* ws, hipStream_t s) {
-  if (elem_bytes == 2) {
-    const Geo g = make_geo<uint16_t>(M, C, kTargetBlocks);
-    hipLaunchKernelGGL(bn_stats_kernel<uint16_t>, dim3(g.gx, g.gy), dim3(kBlock), 0, s, static_cast<const uint16_t*>(x), M,
-                       C, g, ws, ws + (int64_t)g.gy * C);
-  } else {
-    const Geo g = make_geo<float>(M, C, kTargetBlocks);
-    hipLaunchKernelGGL(bn_stats_kernel<float>, dim3(g.gx, g.gy), dim3(kBlock), 0, s, static_cast<const float*>(x), M, C,
-                       g, ws, ws + (int64_t)g.gy * C);
-  }
-}
-
-void bn_act_forward(const void* x, const void* res, void* y, uint8_t* mask, int64_t M, int C, int elem_bytes,
-                    const float* w, const float* b, float eps, float momentum, float* run_mean, float* run_var,
-                    float* save_mean, float* save_invstd, float* scale, float* shift, float* ws, int relu,
-                    int64_t* nbt, hipStream_t s, void* fin_state, const float* rscale, const float* rshift) {
-  if (elem_bytes == 2)
-    bn_forward_t<uint16_t>((const uint16_t*)x, (const uint16_t*)res, (uint16_t*)y, mask, M, C, w, b, eps, momentum,
-                           run_mean, run_var, save_mean, save_invstd, scale, shift, ws, relu, nbt, fin_state, s,
-                           rscale, rshift);
+  // generic k, s: per-pixel gather (latency-bound: more workgroups than the plain BN passes)
+  if ((pg.k + pg.s - 1) / pg.s <= 2)
+    bn_backward_src<T>(DyPool<T, TWIN, 2>{dy, dy2, amax, pg}, x, dx, (T*)nullptr, sh, bs, ws, nullptr, s,
+                       kPoolTargetBlocks);
   else
-    bn_forward_t<float>((const float*)x, (const float*)res, (float*)y, mask, M, C, w, b, eps, momentum, run_mean,
-                        run_var, save_mean, save_invstd, scale, shift, ws, relu, nbt, fin_state, s, rscale, rshift);
+    bn_backward_src<T>(DyPool<T, TWIN, 0>{dy, dy2, amax, pg}, x, dx, (T*)nullptr, sh, bs, ws, nullptr, s,
+                       kPoolTargetBlocks);
+}
+
+}  // namespace
+
+size_t bn_fin_state_bytes(int C) { return kFinStateFlagsOffset + sizeof(uint32_t) * (size_t)((C + kFinC - 1) / kFinC); }
+
+size_t bn_workspace_floats(int64_t M, int C, int elem_bytes) {
+  // sized for the larger (pool-backward) grid so one workspace fits every pass
+  size_t n = 0;
+  with_elem(elem_bytes, [&](auto t) { n = (size_t)2 * make_geo<decltype(t)>(M, C, kPoolTargetBlocks).gy * C; });
+  return n;
+}
+
+void bn_set_blocks(int blocks) { g_bn_blocks = blocks < 64 ? 64 : blocks > kPoolTargetBlocks ? kPoolTargetBlocks : blocks; }
+
+// elements of a thread's 16-byte channel vector (Vec<T>::N)
+static int vec_elems(int elem_bytes) { return elem_bytes == 2 ? 8 : 4; }
+
+bool bn_supported(int C, int elem_bytes) { return C % vec_elems(elem_bytes) == 0 && C >= vec_elems(elem_bytes); }
+
+size_t bn_mask_bytes(int64_t M, int C, int elem_bytes) { return (size_t)M * (size_t)(C / vec_elems(elem_bytes)); }
+
+void bn_stats_partials(BnShape sh, const void* x, float* ws, hipStream_t s) {
+  with_elem(sh.elem_bytes, [&](auto t) { stats_partials(sh, (const decltype(t)*)x, BnPartials{}, ws, s); });
+}
+
+void bn_act_forward(BnShape sh, const void* x, BnResidual res, void* y, uint8_t* mask, const BnFwdStats& st,
+                    BnPartials pre, float* ws, int relu, void* fin_state, hipStream_t s) {
+  with_elem(sh.elem_bytes, [&](auto t) {
+    using T = decltype(t);
+    const Geo g = make_geo<T>(sh.M, sh.C, g_bn_blocks);
+    // the deferred-residual apply has no in-launch finalize form
+    const FinSync fs = make_fin(res.rscale ? nullptr : fin_state, g, sh.C, s);
+    const FwdFin ff = fwd_fin(st, stats_partials(sh, (const T*)x, pre, ws, s));
+    if (!fs.ticket) launch_finalize(ff, sh.M, sh.C, s);
+    launch_apply<T>((const T*)x, res, (T*)y, mask, sh, g, relu, fs, ff, s);
+  });
 }
 
 // Statistics (or the producer's partials) + finalize only: the BN whose apply
 // pass is deferred into its consumer (bn_apply_kernel RBN).
-void bn_act_finalize(const void* x, int64_t M, int C, int elem_bytes, const float* psum, const float* psq, int gy,
-                     const float* w, const float* b, float eps, float momentum, float* run_mean, float* run_var,
-                     float* save_mean, float* save_invstd, float* scale, float* shift, float* ws, int64_t* nbt,
-                     hipStream_t s) {
-  if (!psum) {
-    if (elem_bytes == 2)
-      bn_stats_t<uint16_t>((const uint16_t*)x, M, C, w, b, eps, momentum, run_mean, run_var, save_mean, save_invstd,
-                           scale, shift, ws, nbt, s);
-    else
-      bn_stats_t<float>((const float*)x, M, C, w, b, eps, momentum, run_mean, run_var, save_mean, save_invstd, scale,
-                        shift, ws, nbt, s);
-    return;
-  }
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + kFinC - 1) / kFinC), dim3(kBlock), 0, s, psum, psq, gy, M, C, w, b,
-                     eps, momentum, run_mean, run_var, save_mean, save_invstd, scale, shift, nbt);
+void bn_act_finalize(BnShape sh, const void* x, const BnFwdStats& st, BnPartials pre, float* ws, hipStream_t s) {
+  with_elem(sh.elem_bytes, [&](auto t) {
+    launch_finalize(fwd_fin(st, stats_partials(sh, (const decltype(t)*)x, pre, ws, s)), sh.M, sh.C, s);
+  });
 }
 
-template <typename T>
-void bn_forward_pre_t(const T* x, const T* res, T* y, uint8_t* mask, int64_t M, int C, const float* psum,
-                      const float* psq, int gy, const float* w, const float* b, float eps, float momentum,
-                      float* run_mean, float* run_var, float* save_mean, float* save_invstd, float* scale, float* shift,
-                      int relu, int64_t* nbt, void* fin_state, hipStream_t s, const float* rscale = nullptr,
-                      const float* rshift = nullptr) {
-  const Geo g = make_geo<T>(M, C, kTargetBlocks);
-  if (rscale) fin_state = nullptr;
-  const FinSync fs = make_fin(fin_state, g, C, s);
-  const FwdFin ff{psum, psq, gy, w, b, eps, momentum, run_mean, run_var, save_mean, save_invstd, scale, shift, nbt};
-  if (!fs.ticket)
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + kFinC - 1) / kFinC), dim3(kBlock), 0, s, psum, psq, gy, M, C, w,
-                       b, eps, momentum, run_mean, run_var, save_mean, save_invstd, scale, shift, nbt);
-  launch_apply<T>(x, res, y, mask, M, C, g, scale, shift, relu, fs, ff, s, rscale, rshift);
+void bn_act_backward(BnShape sh, const void* dy, const void* dy2, const uint8_t* mask, const void* x, void* dx,
+                     void* dres, const BnBwdStats& bs, float* ws, int relu, void* fin_state, hipStream_t s) {
+  with_elem(sh.elem_bytes, [&](auto t) {
+    using T = decltype(t);
+    with_dy((const T*)dy, (const T*)dy2, mask, relu, [&](auto src) {
+      if (!(dy2 && dres)) return bn_backward_src<T>(src, (const T*)x, (T*)dx, (T*)dres, sh, bs, ws, fin_state, s);
+      // twin + residual (ResNet block output): the reduce pass writes dz = dres
+      // and the apply pass reads it back (one tensor instead of dy, dy2, mask)
+      const Geo g = make_geo<T>(sh.M, sh.C, g_bn_blocks);
+      const WsParts p = ws_parts(ws, g, sh.C);
+      launch_reduce<T, true>(src, (const T*)x, sh, g, bs, p, s, (T*)dres);
+      bn_backward_dz<T>((const T*)dres, (const T*)x, (T*)dx, sh, g, bs, bwd_fin(bs, p), fin_state, s);
+    });
+  });
 }
 
-void bn_act_forward_pre(const void* x, const void* res, void* y, uint8_t* mask, int64_t M, int C, int elem_bytes,
-                        const float* psum, const float* psq, int gy, const float* w, const float* b, float eps, float momentum,
-                        float* run_mean, float* run_var, float* save_mean, float* save_invstd, float* scale,
-                        float* shift, int relu, int64_t* nbt, hipStream_t s, void* fin_state, const float* rscale,
-                        const float* rshift) {
-  if (elem_bytes == 2)
-    bn_forward_pre_t<uint16_t>((const uint16_t*)x, (const uint16_t*)res, (uint16_t*)y, mask, M, C, psum, psq, gy, w,
-                               b, eps, momentum, run_mean, run_var, save_mean, save_invstd, scale, shift, relu, nbt,
-                               fin_state, s, rscale, rshift);
-  else
-    bn_forward_pre_t<float>((const float*)x, (const float*)res, (float*)y, mask, M, C, psum, psq, gy, w, b, eps,
-                            momentum, run_mean, run_var, save_mean, save_invstd, scale, shift, relu, nbt, fin_state, s,
-                            rscale, rshift);
-}
-
-void bn_act_backward(const void* dy, const void* dy2, const uint8_t* mask, const void* x, void* dx, void* dres,
-                     int64_t M, int C, int elem_bytes, const float* w, const float* mean, const float* invstd,
-                     float* dgamma, float* dbeta, float* ws, int relu, float* gw_acc, float* gb_acc, hipStream_t s,
-                     void* fin_state) {
-  if (elem_bytes == 2)
-    bn_backward_t<uint16_t>((const uint16_t*)dy, (const uint16_t*)dy2, mask, (const uint16_t*)x, (uint16_t*)dx,
-                            (uint16_t*)dres, M, C, w, mean, invstd, dgamma, dbeta, ws, relu, gw_acc, gb_acc, fin_state,
-                            s);
-  else
-    bn_backward_t<float>((const float*)dy, (const float*)dy2, mask, (const float*)x, (float*)dx, (float*)dres, M, C, w,
-                         mean, invstd, dgamma, dbeta, ws, relu, gw_acc, gb_acc, fin_state, s);
-}
-
-// dz (already gated and twin-summed) and its partials sum(dz), sum(dz*(x-mean))
+// dz (already gated and twin-summed) and its partials sum(dz), sum(dz*x)
 // [2][gy][C] from the consuming convolution's grad-input epilogue (gemm.hip
 // BnBwd): no reduction pass, only finalize + apply.
-template <typename T>
-void bn_bwd_apply_pre_t(const T* dz, const T* x, T* dx, int64_t M, int C, const float* w, const float* mean,
-                        const float* invstd, float* dgamma, float* dbeta, const float* pdb, const float* pdg, int gy,
-                        float* gw_acc, float* gb_acc, void* fin_state, hipStream_t s) {
-  const Geo g = make_geo<T>(M, C, kTargetBlocks);
-  const FinSync fs = make_fin(fin_state, g, C, s);
-  const BwdFin bf{pdb, pdg, gy, dbeta, dgamma, gb_acc, gw_acc, mean, invstd};
-  launch_bwd_apply<T, DyPlain<T, false, false>, false>(DyPlain<T, false, false>{dz, nullptr, nullptr}, x, dx,
-                                                       (T*)nullptr, M, C, g, w, mean, invstd, bf, fs, s);
+void bn_act_backward_pre(BnShape sh, const void* dz, const void* x, void* dx, const BnBwdStats& bs, BnPartials part,
+                         void* fin_state, hipStream_t s) {
+  with_elem(sh.elem_bytes, [&](auto t) {
+    using T = decltype(t);
+    const Geo g = make_geo<T>(sh.M, sh.C, g_bn_blocks);
+    bn_backward_dz<T>((const T*)dz, (const T*)x, (T*)dx, sh, g, bs, bwd_fin(bs, part, true), fin_state, s);
+  });
 }
 
-void bn_bwd_finalize_lazy(const float* pdb, const float* pdg, int gy, int64_t M, int C, int elem_bytes, int center,
-                          const float* w, const float* mean, const float* invstd, float* dgamma, float* dbeta,
-                          float* gw_acc, float* gb_acc, float* coef, void* padz, void* padx, hipStream_t s) {
-  const dim3 grid((C + kFinC - 1) / kFinC);
-  if (elem_bytes == 2)
-    hipLaunchKernelGGL(bn_bwd_finalize_lazy_kernel<uint16_t>, grid, dim3(kBlock), 0, s, pdb, pdg, gy, C, M, center, w,
-                       mean, invstd, dbeta, dgamma, gb_acc, gw_acc, reinterpret_cast<float4*>(coef),
-                       static_cast<uint16_t*>(padz), static_cast<uint16_t*>(padx));
-  else
-    hipLaunchKernelGGL(bn_bwd_finalize_lazy_kernel<float>, grid, dim3(kBlock), 0, s, pdb, pdg, gy, C, M, center, w,
-                       mean, invstd, dbeta, dgamma, gb_acc, gw_acc, reinterpret_cast<float4*>(coef),
-                       static_cast<float*>(padz), static_cast<float*>(padx));
+void bn_bwd_finalize_lazy(BnShape sh, BnPartials part, int center, const BnBwdStats& bs, BnLazyOut lazy,
+                          hipStream_t s) {
+  with_elem(sh.elem_bytes, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(bn_bwd_finalize_lazy_kernel<T>, fin_grid(sh.C), dim3(kBlock), 0, s, part.a, part.b, part.gy,
+                       sh.C, sh.M, center, bs.w, bs.mean, bs.invstd, bs.dbeta, bs.dgamma, bs.gb_acc, bs.gw_acc,
+                       reinterpret_cast<float4*>(lazy.coef), static_cast<T*>(lazy.padz), static_cast<T*>(lazy.padx));
+  });
 }
 
 // Full (unlinked) backward without the apply pass: the reduce pass writes dz
 // (ReLU-masked, twin-summed dy) and the partials; the finalize emits the lazy
 // coefficients.  dz doubles as the residual gradient.
-template <typename T>
-void bn_backward_lazy_t(const T* dy, const T* dy2, const uint8_t* mask, const T* x, T* dz, int64_t M, int C,
-                        const float* w, const float* mean, const float* invstd, float* dgamma, float* dbeta, float* ws,
-                        int relu, float* gw_acc, float* gb_acc, float* coef, void* padz, void* padx, hipStream_t s) {
-  const Geo g = make_geo<T>(M, C, kTargetBlocks);
-  float* pdb = ws;
-  float* pdg = ws + (int64_t)g.gy * C;
-#define GK_RED(R, TW)                                                                                              \
-  hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, DyPlain<T, R, TW>, true>), dim3(g.gx, g.gy), dim3(kBlock), 0, s,      \
-                     DyPlain<T, R, TW>{dy, dy2, mask}, x, M, C, g, mean, invstd, pdb, pdg, dz)
-  if (relu && dy2) GK_RED(true, true);
-  else if (relu) GK_RED(true, false);
-  else if (dy2) GK_RED(false, true);
-  else GK_RED(false, false);
-#undef GK_RED
-  bn_bwd_finalize_lazy(pdb, pdg, g.gy, M, C, sizeof(T), 0, w, mean, invstd, dgamma, dbeta, gw_acc, gb_acc, coef,
-                       padz, padx, s);
+void bn_act_backward_lazy(BnShape sh, const void* dy, const void* dy2, const uint8_t* mask, const void* x, void* dz,
+                          const BnBwdStats& bs, float* ws, int relu, BnLazyOut lazy, hipStream_t s) {
+  with_elem(sh.elem_bytes, [&](auto t) {
+    using T = decltype(t);
+    const Geo g = make_geo<T>(sh.M, sh.C, g_bn_blocks);
+    const WsParts p = ws_parts(ws, g, sh.C);
+    with_dy((const T*)dy, (const T*)dy2, mask, relu,
+            [&](auto src) { launch_reduce<T, true>(src, (const T*)x, sh, g, bs, p, s, (T*)dz); });
+    bn_bwd_finalize_lazy(sh, p, 0, bs, lazy, s);
+  });
 }
 
-void bn_act_backward_lazy(const void* dy, const void* dy2, const uint8_t* mask, const void* x, void* dz, int64_t M,
-                          int C, int elem_bytes, const float* w, const float* mean, const float* invstd,
-                          float* dgamma, float* dbeta, float* ws, int relu, float* gw_acc, float* gb_acc, float* coef,
-                          void* padz, void* padx, hipStream_t s) {
-  if (elem_bytes == 2)
-    bn_backward_lazy_t<uint16_t>((const uint16_t*)dy, (const uint16_t*)dy2, mask, (const uint16_t*)x, (uint16_t*)dz,
-                                 M, C, w, mean, invstd, dgamma, dbeta, ws, relu, gw_acc, gb_acc, coef, padz, padx, s);
-  else
-    bn_backward_lazy_t<float>((const float*)dy, (const float*)dy2, mask, (const float*)x, (float*)dz, M, C, w, mean,
-                              invstd, dgamma, dbeta, ws, relu, gw_acc, gb_acc, coef, padz, padx, s);
-}
 
 // Materialise a lazy dx (a consumer that cannot take the lazy operand):
 // dx = k1 * ((dz - k2) - (x - mu) * k4) from the coefficient table.
@@ -1389,185 +1368,61 @@ __global__ __launch_bounds__(kBlock) void bn_lazy_apply_kernel(const T* __restri
   }
 }
 
-void bn_lazy_apply(const void* dz, const void* x, void* dx, int64_t M, int C, int elem_bytes, const float* coef,
-                   hipStream_t s) {
-  if (elem_bytes == 2) {
-    const Geo g = make_geo<uint16_t>(M, C, kTargetBlocks);
-    hipLaunchKernelGGL(bn_lazy_apply_kernel<uint16_t>, dim3(g.gx, g.gy), dim3(kBlock), 0, s, (const uint16_t*)dz,
-                       (const uint16_t*)x, (uint16_t*)dx, M, C, g, reinterpret_cast<const float4*>(coef));
-  } else {
-    const Geo g = make_geo<float>(M, C, kTargetBlocks);
-    hipLaunchKernelGGL(bn_lazy_apply_kernel<float>, dim3(g.gx, g.gy), dim3(kBlock), 0, s, (const float*)dz,
-                       (const float*)x, (float*)dx, M, C, g, reinterpret_cast<const float4*>(coef));
-  }
+void bn_lazy_apply(BnShape sh, const void* dz, const void* x, void* dx, const float* coef, hipStream_t s) {
+  with_elem(sh.elem_bytes, [&](auto t) {
+    using T = decltype(t);
+    const Geo g = make_geo<T>(sh.M, sh.C, g_bn_blocks);
+    hipLaunchKernelGGL(bn_lazy_apply_kernel<T>, grid_of(g), dim3(kBlock), 0, s, (const T*)dz, (const T*)x, (T*)dx, sh.M,
+                       sh.C, g, reinterpret_cast<const float4*>(coef));
+  });
 }
 
 // Linked backward (dz + partials from the consumer's GEMM epilogue) of a BN
 // whose residual was a deferred BN of x2 (bn_apply_kernel RBN): the second
 // BN's reduce pass over (dz, x2) and both finalizes, then ONE apply pass
 // writing dx and dx2 (dz read once).
-template <typename T>
-void bn_bwd_pre_dual_t(const T* dz, const T* x, T* dx, int64_t M, int C, const float* w, const float* mean,
-                       const float* invstd, float* dgamma, float* dbeta, const float* pdb, const float* pdg, int gy,
-                       float* gw_acc, float* gb_acc, const T* x2, T* dx2, const float* w2, const float* mean2,
-                       const float* invstd2, float* dgamma2, float* dbeta2, float* ws2, float* gw2_acc,
-                       float* gb2_acc, hipStream_t s) {
-  const Geo g = make_geo<T>(M, C, kTargetBlocks);
-  float* pdb2 = ws2;
-  float* pdg2 = ws2 + (int64_t)g.gy * C;
-  using Src = DyPlain<T, false, false>;
-  const Src src{dz, nullptr, nullptr};
-  hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, Src>), dim3(g.gx, g.gy), dim3(kBlock), 0, s, src, x2, M, C, g, mean2,
-                     invstd2, pdb2, pdg2, (T*)nullptr);
-  const dim3 fg((C + kFinC - 1) / kFinC);
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, fg, dim3(kBlock), 0, s, pdb2, pdg2, g.gy, C, dbeta2, dgamma2, gb2_acc,
-                     gw2_acc, nullptr, nullptr);
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, fg, dim3(kBlock), 0, s, pdb, pdg, gy, C, dbeta, dgamma, gb_acc, gw_acc,
-                     mean, invstd);
-  const BwdDual<T> d2{x2, dx2, w2, mean2, invstd2, dbeta2, dgamma2};
-  hipLaunchKernelGGL((bn_bwd_apply_kernel<T, Src, false, false, kBnUnroll, true>), dim3(g.gx, g.gy), dim3(kBlock), 0,
-                     s, src, x, dx, (T*)nullptr, M, C, g, w, mean, invstd, dbeta, dgamma, FinSync{}, BwdFin{}, d2);
-}
-
-void bn_act_backward_pre_dual(const void* dz, const void* x, void* dx, int64_t M, int C, int elem_bytes,
-                              const float* w, const float* mean, const float* invstd, float* dgamma, float* dbeta,
-                              const float* pdb, const float* pdg, int gy, float* gw_acc, float* gb_acc, const void* x2,
-                              void* dx2, const float* w2, const float* mean2, const float* invstd2, float* dgamma2,
-                              float* dbeta2, float* ws2, float* gw2_acc, float* gb2_acc, hipStream_t s) {
-  if (elem_bytes == 2)
-    bn_bwd_pre_dual_t<uint16_t>((const uint16_t*)dz, (const uint16_t*)x, (uint16_t*)dx, M, C, w, mean, invstd, dgamma,
-                                dbeta, pdb, pdg, gy, gw_acc, gb_acc, (const uint16_t*)x2, (uint16_t*)dx2, w2, mean2,
-                                invstd2, dgamma2, dbeta2, ws2, gw2_acc, gb2_acc, s);
-  else
-    bn_bwd_pre_dual_t<float>((const float*)dz, (const float*)x, (float*)dx, M, C, w, mean, invstd, dgamma, dbeta, pdb,
-                             pdg, gy, gw_acc, gb_acc, (const float*)x2, (float*)dx2, w2, mean2, invstd2, dgamma2,
-                             dbeta2, ws2, gw2_acc, gb2_acc, s);
-}
-
-void bn_act_backward_pre(const void* dz, const void* x, void* dx, int64_t M, int C, int elem_bytes, const float* w,
-                         const float* mean, const float* invstd, float* dgamma, float* dbeta, const float* pdb,
-                         const float* pdg, int gy, float* gw_acc, float* gb_acc, hipStream_t s, void* fin_state) {
-  if (elem_bytes == 2)
-    bn_bwd_apply_pre_t<uint16_t>((const uint16_t*)dz, (const uint16_t*)x, (uint16_t*)dx, M, C, w, mean, invstd, dgamma,
-                                 dbeta, pdb, pdg, gy, gw_acc, gb_acc, fin_state, s);
-  else
-    bn_bwd_apply_pre_t<float>((const float*)dz, (const float*)x, (float*)dx, M, C, w, mean, invstd, dgamma, dbeta, pdb,
-                              pdg, gy, gw_acc, gb_acc, fin_state, s);
+void bn_act_backward_pre_dual(BnShape sh, const void* dz, const void* x, void* dx, const BnBwdStats& bs,
+                              BnPartials part, const void* x2, void* dx2, const BnBwdStats& bs2, float* ws2,
+                              hipStream_t s) {
+  with_elem(sh.elem_bytes, [&](auto t) {
+    using T = decltype(t);
+    using Src = DyPlain<T, false, false>;
+    const Geo g = make_geo<T>(sh.M, sh.C, g_bn_blocks);
+    const WsParts p2 = ws_parts(ws2, g, sh.C);
+    const Src src{(const T*)dz, nullptr, nullptr};
+    launch_reduce<T>(src, (const T*)x2, sh, g, bs2, p2, s);
+    launch_bwd_finalize(bwd_fin(bs2, p2), sh.C, s);
+    launch_bwd_finalize(bwd_fin(bs, part, true), sh.C, s);
+    const BwdDual<T> d2{(const T*)x2, (T*)dx2, bs2.w, bs2.mean, bs2.invstd, bs2.dbeta, bs2.dgamma};
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<T, Src, false, false, kBnUnroll, true>), grid_of(g), dim3(kBlock), 0, s,
+                       src, (const T*)x, (T*)dx, (T*)nullptr, sh.M, sh.C, g, bs.w, bs.mean, bs.invstd, bs.dbeta,
+                       bs.dgamma, FinSync{}, BwdFin{}, d2);
+  });
 }
 
 // ---------------------------------------------------------------------------
 // BN + ReLU + max-pool
 // ---------------------------------------------------------------------------
-void bn_relu_pool_forward(const void* x, void* y, uint8_t* amax, int64_t N, int C, PoolGeo pg, int elem_bytes,
-                          const float* w, const float* b, float eps, float momentum, float* run_mean, float* run_var,
-                          float* save_mean, float* save_invstd, float* scale, float* shift, float* ws, int64_t* nbt,
-                          hipStream_t s) {
-  const int64_t M = N * pg.H * pg.W;
-  const int64_t P = N * pg.OH * pg.OW;
-  const int V = elem_bytes == 2 ? 8 : 4;
-  const int64_t threads = P * (C / V);
-  const dim3 grid((unsigned)((threads + kBlock - 1) / kBlock));
-  if (elem_bytes == 2) {
-    bn_stats_t<uint16_t>((const uint16_t*)x, M, C, w, b, eps, momentum, run_mean, run_var, save_mean, save_invstd,
-                         scale, shift, ws, nbt, s);
-    if (pg.k == 3 && pg.p == 1)
-      hipLaunchKernelGGL((bn_relu_pool_kernel<uint16_t, 3>), grid, dim3(kBlock), 0, s, (const uint16_t*)x, (uint16_t*)y,
-                         amax, P, C, pg, scale, shift);
-    else
-      hipLaunchKernelGGL(bn_relu_pool_kernel<uint16_t>, grid, dim3(kBlock), 0, s, (const uint16_t*)x, (uint16_t*)y, amax,
-                         P, C, pg, scale, shift);
-  } else {
-    bn_stats_t<float>((const float*)x, M, C, w, b, eps, momentum, run_mean, run_var, save_mean, save_invstd, scale,
-                       shift, ws, nbt, s);
-    if (pg.k == 3 && pg.p == 1)   // all 9 window loads in flight
-      hipLaunchKernelGGL((bn_relu_pool_kernel<float, 3>), grid, dim3(kBlock), 0, s, (const float*)x, (float*)y, amax, P,
-                         C, pg, scale, shift);
-    else
-      hipLaunchKernelGGL(bn_relu_pool_kernel<float>, grid, dim3(kBlock), 0, s, (const float*)x, (float*)y, amax, P, C,
-                         pg, scale, shift);
-  }
-}
-
-// statistics pre-reduced by the producing convolution (stem.hip / stem_f32.hip
+// pre: statistics pre-reduced by the producing convolution (stem.hip / stem_f32.hip
 // epilogues): finalize + the fused BN / ReLU / max-pool pass only
-void bn_relu_pool_forward_pre(const void* x, void* y, uint8_t* amax, int64_t N, int C, PoolGeo pg, int elem_bytes,
-                              const float* psum, const float* psq, int gy, const float* w, const float* b, float eps,
-                              float momentum, float* run_mean, float* run_var, float* save_mean, float* save_invstd,
-                              float* scale, float* shift, int64_t* nbt, hipStream_t s) {
-  const int64_t M = N * pg.H * pg.W;
-  const int64_t P = N * pg.OH * pg.OW;
-  const int64_t threads = P * (C / (elem_bytes == 2 ? 8 : 4));
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + kFinC - 1) / kFinC), dim3(kBlock), 0, s, psum, psq, gy, M, C, w, b,
-                     eps, momentum, run_mean, run_var, save_mean, save_invstd, scale, shift, nbt);
-  const dim3 grid((unsigned)((threads + kBlock - 1) / kBlock));
-  if (elem_bytes == 4 && pg.k == 3 && pg.p == 1)
-    hipLaunchKernelGGL((bn_relu_pool_kernel<float, 3>), grid, dim3(kBlock), 0, s, (const float*)x, (float*)y, amax, P, C,
-                       pg, scale, shift);
-  else if (elem_bytes == 4)
-    hipLaunchKernelGGL(bn_relu_pool_kernel<float>, grid, dim3(kBlock), 0, s, (const float*)x, (float*)y, amax, P, C, pg,
-                       scale, shift);
-  else if (pg.k == 3 && pg.p == 1)
-    hipLaunchKernelGGL((bn_relu_pool_kernel<uint16_t, 3>), grid, dim3(kBlock), 0, s, (const uint16_t*)x, (uint16_t*)y,
-                       amax, P, C, pg, scale, shift);
-  else
-    hipLaunchKernelGGL(bn_relu_pool_kernel<uint16_t>, grid, dim3(kBlock), 0, s, (const uint16_t*)x, (uint16_t*)y, amax,
-                       P, C, pg, scale, shift);
+void bn_relu_pool_forward(BnShape sh, PoolGeo pg, const void* x, void* y, uint8_t* amax, const BnFwdStats& st,
+                          BnPartials pre, float* ws, hipStream_t s) {
+  with_elem(sh.elem_bytes, [&](auto t) {
+    using T = decltype(t);
+    launch_finalize(fwd_fin(st, stats_partials(sh, (const T*)x, pre, ws, s)), sh.M, sh.C, s);
+    launch_pool<T>((const T*)x, (T*)y, amax, sh, pg, st.scale, st.shift, s);
+  });
 }
 
-template <typename T, bool TWIN>
-void bn_pool_backward_tw(const T* dy, const T* dy2, const uint8_t* amax, const T* x, T* dx, int64_t M, int C,
-                         PoolGeo pg, const float* w, const float* mean, const float* invstd, float* dgamma,
-                         float* dbeta, float* ws, float* gw_acc, float* gb_acc, hipStream_t s) {
-  const int TH = (pg.H + pg.p + pg.s - 1) / pg.s, TW = (pg.W + pg.p + pg.s - 1) / pg.s;
-  const int64_t ntiles = M / ((int64_t)pg.H * pg.W) * TH * TW;
-  // every window reaching tile th has oh in {th-1, th}.  ntiles <= M: the workspace holds the partials of a
-  // grid over M rows (bn_workspace_floats); a 1-pixel-wide plane under a padded pool has more tiles than
-  // pixels and would get more row chunks than that, so it takes the per-pixel gather.
-  if (pg.s == 2 && pg.k <= 4 && ntiles <= M) {
-    // tile-ordered fast path (3x3/s2 stem pool)
-    const Geo g = make_geo<T>(ntiles, C, kPoolTargetBlocks);
-    float* pdb = ws;
-    float* pdg = ws + (int64_t)g.gy * C;
-    hipLaunchKernelGGL((bn_pool_tile_kernel<T, TWIN, false>), dim3(g.gx, g.gy), dim3(kBlock), 0, s, dy, dy2, amax, x,
-                       (T*)nullptr, ntiles, C, pg, TH, TW, g, M, w, mean, invstd, (const float*)nullptr,
-                       (const float*)nullptr, pdb, pdg);
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + kFinC - 1) / kFinC), dim3(kBlock), 0, s, pdb, pdg, g.gy, C,
-                       dbeta, dgamma, gb_acc, gw_acc);
-    hipLaunchKernelGGL((bn_pool_tile_kernel<T, TWIN, true>), dim3(g.gx, g.gy), dim3(kBlock), 0, s, dy, dy2, amax, x,
-                       dx, ntiles, C, pg, TH, TW, g, M, w, mean, invstd, dbeta, dgamma, (float*)nullptr,
-                       (float*)nullptr);
-    return;
-  }
-  // generic k, s: per-pixel gather (latency-bound: more workgroups than the plain BN passes)
-  if ((pg.k + pg.s - 1) / pg.s <= 2)
-    bn_backward_src<T>(DyPool<T, TWIN, 2>{dy, dy2, amax, pg}, x, dx, (T*)nullptr, M, C, w, mean, invstd, dgamma,
-                       dbeta, ws, gw_acc, gb_acc, nullptr, s, kPoolTargetBlocks);
-  else
-    bn_backward_src<T>(DyPool<T, TWIN, 0>{dy, dy2, amax, pg}, x, dx, (T*)nullptr, M, C, w, mean, invstd, dgamma,
-                       dbeta, ws, gw_acc, gb_acc, nullptr, s, kPoolTargetBlocks);
-}
-
-template <typename T>
-void bn_pool_backward_t(const T* dy, const T* dy2, const uint8_t* amax, const T* x, T* dx, int64_t M, int C, PoolGeo pg,
-                        const float* w, const float* mean, const float* invstd, float* dgamma, float* dbeta, float* ws,
-                        float* gw_acc, float* gb_acc, hipStream_t s) {
-  if (dy2)
-    bn_pool_backward_tw<T, true>(dy, dy2, amax, x, dx, M, C, pg, w, mean, invstd, dgamma, dbeta, ws, gw_acc, gb_acc, s);
-  else
-    bn_pool_backward_tw<T, false>(dy, dy2, amax, x, dx, M, C, pg, w, mean, invstd, dgamma, dbeta, ws, gw_acc, gb_acc,
-                                  s);
-}
-
-void bn_relu_pool_backward(const void* dy, const void* dy2, const uint8_t* amax, const void* x, void* dx, int64_t N,
-                           int C, PoolGeo pg, int elem_bytes, const float* w, const float* mean, const float* invstd,
-                           float* dgamma, float* dbeta, float* ws, float* gw_acc, float* gb_acc, hipStream_t s) {
-  const int64_t M = N * pg.H * pg.W;
-  if (elem_bytes == 2)
-    bn_pool_backward_t<uint16_t>((const uint16_t*)dy, (const uint16_t*)dy2, amax, (const uint16_t*)x, (uint16_t*)dx, M,
-                                 C, pg, w, mean, invstd, dgamma, dbeta, ws, gw_acc, gb_acc, s);
-  else
-    bn_pool_backward_t<float>((const float*)dy, (const float*)dy2, amax, (const float*)x, (float*)dx, M, C, pg, w, mean,
-                              invstd, dgamma, dbeta, ws, gw_acc, gb_acc, s);
+void bn_relu_pool_backward(BnShape sh, PoolGeo pg, const void* dy, const void* dy2, const uint8_t* amax,
+                           const void* x, void* dx, const BnBwdStats& bs, float* ws, hipStream_t s) {
+  with_elem(sh.elem_bytes, [&](auto t) {
+    using T = decltype(t);
+    if (dy2)
+      bn_pool_backward_tw<T, true>((const T*)dy, (const T*)dy2, amax, (const T*)x, (T*)dx, sh, pg, bs, ws, s);
+    else
+      bn_pool_backward_tw<T, false>((const T*)dy, (const T*)dy2, amax, (const T*)x, (T*)dx, sh, pg, bs, ws, s);
+  });
 }
 
 }  // namespace gk

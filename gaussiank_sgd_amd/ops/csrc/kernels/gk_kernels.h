@@ -300,6 +300,30 @@ void clip_grad_norm(float* g, int64_t n, float max_norm, double* ws, float* coef
 // Fused batch norm (training) + residual add + ReLU, channels-last [M, C].
 // elem_bytes: 2 (bf16) or 4 (fp32).  ws: bn_workspace_floats() floats.
 // ---------------------------------------------------------------------------
+// The argument groups of the entry points below: plain aggregates, per-channel
+// pointers fp32[C]; "opt" ones may be nullptr.
+struct BnShape { int64_t M; int C; int elem_bytes; };   // activations viewed as [M, C]
+// Per-row-chunk partial sums, [gy][C] each (a == nullptr: none).  Forward: sum(x), sum(x^2);
+// backward: sum(dz), sum(dz * xhat) -- or sum(dz * x) where they come from a GEMM epilogue.
+struct BnPartials { const float* a; const float* b; int gy; };
+// Parameters in (w, b: opt); running statistics (opt), saved batch statistics and the apply
+// coefficients scale = gamma * invstd, shift = beta - mean * scale out; nbt (opt): num_batches_tracked.
+struct BnFwdStats {
+  const float* w; const float* b;
+  float eps, momentum;
+  float* run_mean; float* run_var; float* save_mean; float* save_invstd; float* scale; float* shift;
+  int64_t* nbt;
+};
+// The forward's saved statistics in (w: opt), parameter gradients out; gw_acc / gb_acc (opt):
+// dgamma / dbeta are also added there (the optimizer's gradient arena).
+struct BnBwdStats {
+  const float* w; const float* mean; const float* invstd;
+  float* dgamma; float* dbeta; float* gw_acc; float* gb_acc;
+};
+// res (opt): added before the ReLU.  rscale / rshift (opt, with res): the residual is a batch-normalised
+// tensor whose apply was deferred here -- res * rscale + rshift is added.
+struct BnResidual { const void* res; const float* rscale; const float* rshift; };
+struct BnLazyOut { float* coef; void* padz; void* padx; };   // see "Lazy BN backward" below
 size_t bn_workspace_floats(int64_t M, int C, int elem_bytes);
 // fin_state (optional, bn_fin_state_bytes(C), zero-initialised once, kept per
 // layer): the finalize of the statistics runs inside the apply pass that
@@ -313,33 +337,16 @@ size_t bn_mask_bytes(int64_t M, int C, int elem_bytes);
 // the statistics pass of bn_act_forward alone (per-block sum / sum-of-squares
 // partials into ws): what a convolution without the statistics epilogue costs
 // the BN that consumes it (the autotuner times MIOpen candidates with it)
-void bn_stats_partials(const void* x, int64_t M, int C, int elem_bytes, float* ws, hipStream_t s);
-void bn_act_forward(const void* x, const void* res, void* y, uint8_t* mask, int64_t M, int C, int elem_bytes,
-                    const float* w, const float* b, float eps, float momentum, float* run_mean, float* run_var,
-                    float* save_mean, float* save_invstd, float* scale, float* shift, float* ws, int relu,
-                    int64_t* nbt, hipStream_t stream, void* fin_state = nullptr, const float* rscale = nullptr,
-                    const float* rshift = nullptr);
-// rscale / rshift (optional, with res): the residual is a batch-normalised
-// tensor whose apply was deferred here -- res * rscale + rshift is added.
-// bn_act_finalize: the statistics (psum == nullptr: the stats pass over x;
-// else the producer's [gy][C] partials) and the finalize of a BN whose apply
-// pass is deferred into its consumer; no apply.
-void bn_act_finalize(const void* x, int64_t M, int C, int elem_bytes, const float* psum, const float* psq, int gy,
-                     const float* w, const float* b, float eps, float momentum, float* run_mean, float* run_var,
-                     float* save_mean, float* save_invstd, float* scale, float* shift, float* ws, int64_t* nbt,
-                     hipStream_t stream);
-// dy2 (optional): a second upstream gradient of the same output, summed on load.
-// bn_act_forward with the batch statistics already reduced to per-row
-// partials (psum / psq: [gy][C] each), e.g. by the producing
-// convolution's epilogue (gemm_nt / conv_nt `stats`).
-void bn_act_forward_pre(const void* x, const void* res, void* y, uint8_t* mask, int64_t M, int C, int elem_bytes,
-                        const float* psum, const float* psq, int gy, const float* w, const float* b, float eps, float momentum,
-                        float* run_mean, float* run_var, float* save_mean, float* save_invstd, float* scale,
-                        float* shift, int relu, int64_t* nbt, hipStream_t stream, void* fin_state = nullptr,
-                        const float* rscale = nullptr, const float* rshift = nullptr);
-// dz and its [2][gy][C] partials sum(dz), sum(dz * x) come from a grad-input
-// GEMM's BatchNorm-backward epilogue (BnBwdArgs below); finalize (centring
-// with the mean) + apply only.  bf16 (elem_bytes 2) or fp32 (4).
+void bn_stats_partials(BnShape sh, const void* x, float* ws, hipStream_t stream);
+// pre: the batch statistics already reduced to per-row-chunk partials, e.g. by
+// the producing convolution's epilogue (gemm_nt / conv_nt `stats`, stem.hip):
+// no statistics pass over x, and ws is not touched.
+void bn_act_forward(BnShape sh, const void* x, BnResidual res, void* y, uint8_t* mask, const BnFwdStats& st,
+                    BnPartials pre, float* ws, int relu, void* fin_state, hipStream_t stream);
+// bn_act_finalize: the statistics (pre.a == nullptr: the stats pass over x;
+// else the producer's partials) and the finalize of a BN whose apply pass is
+// deferred into its consumer (BnResidual rscale / rshift); no apply.
+void bn_act_finalize(BnShape sh, const void* x, const BnFwdStats& st, BnPartials pre, float* ws, hipStream_t stream);
 // Lazy BN backward (no apply pass): dx = k1 * ((dz - k2) - (x - mu) * k4) is
 // computed by the consumer GEMMs (gemm.hip LazyA / LazyG) from dz, x and
 // coef[C] = {k1, k2, mu, k4}; padz / padx ([C], activation dtype) are the
@@ -347,52 +354,40 @@ void bn_act_forward_pre(const void* x, const void* res, void* y, uint8_t* mask, 
 //   bn_bwd_finalize_lazy: from [2][gy][C] partials (center: sum(dz*x) form)
 //   bn_act_backward_lazy: full path, the reduce pass writes dz
 //   bn_lazy_apply       : materialise dx (for a consumer without the lazy path)
-void bn_bwd_finalize_lazy(const float* pdb, const float* pdg, int gy, int64_t M, int C, int elem_bytes, int center,
-                          const float* w, const float* mean, const float* invstd, float* dgamma, float* dbeta,
-                          float* gw_acc, float* gb_acc, float* coef, void* padz, void* padx, hipStream_t stream);
-void bn_act_backward_lazy(const void* dy, const void* dy2, const uint8_t* mask, const void* x, void* dz, int64_t M,
-                          int C, int elem_bytes, const float* w, const float* mean, const float* invstd,
-                          float* dgamma, float* dbeta, float* ws, int relu, float* gw_acc, float* gb_acc, float* coef,
-                          void* padz, void* padx, hipStream_t stream);
-void bn_lazy_apply(const void* dz, const void* x, void* dx, int64_t M, int C, int elem_bytes, const float* coef,
-                   hipStream_t stream);
+void bn_bwd_finalize_lazy(BnShape sh, BnPartials part, int center, const BnBwdStats& bs, BnLazyOut lazy,
+                          hipStream_t stream);
+void bn_act_backward_lazy(BnShape sh, const void* dy, const void* dy2, const uint8_t* mask, const void* x, void* dz,
+                          const BnBwdStats& bs, float* ws, int relu, BnLazyOut lazy, hipStream_t stream);
+void bn_lazy_apply(BnShape sh, const void* dz, const void* x, void* dx, const float* coef, hipStream_t stream);
+// bn_act_backward_pre: dz and its partials sum(dz), sum(dz * x) come from a
+// grad-input GEMM's BatchNorm-backward epilogue (BnBwdArgs below); finalize
+// (centring with the mean) + apply only.
+void bn_act_backward_pre(BnShape sh, const void* dz, const void* x, void* dx, const BnBwdStats& bs, BnPartials part,
+                         void* fin_state, hipStream_t stream);
 // bn_act_backward_pre of a BN whose residual was the deferred BN of x2
-// (bn_act_forward rscale / rshift): also that BN's reduce (over dz, x2) and
+// (BnResidual rscale / rshift): also that BN's reduce (over dz, x2) and
 // finalize, and its dx2 written by the same apply pass; ws2 >= bn_workspace_floats.
-void bn_act_backward_pre_dual(const void* dz, const void* x, void* dx, int64_t M, int C, int elem_bytes,
-                              const float* w, const float* mean, const float* invstd, float* dgamma, float* dbeta,
-                              const float* pdb, const float* pdg, int gy, float* gw_acc, float* gb_acc, const void* x2,
-                              void* dx2, const float* w2, const float* mean2, const float* invstd2, float* dgamma2,
-                              float* dbeta2, float* ws2, float* gw2_acc, float* gb2_acc, hipStream_t stream);
-void bn_act_backward_pre(const void* dz, const void* x, void* dx, int64_t M, int C, int elem_bytes, const float* w,
-                         const float* mean, const float* invstd, float* dgamma, float* dbeta, const float* pdb,
-                         const float* pdg, int gy, float* gw_acc, float* gb_acc, hipStream_t stream,
-                         void* fin_state = nullptr);
-void bn_act_backward(const void* dy, const void* dy2, const uint8_t* mask, const void* x, void* dx, void* dres,
-                     int64_t M, int C, int elem_bytes, const float* w, const float* mean, const float* invstd,
-                     float* dgamma, float* dbeta, float* ws, int relu, float* gw_acc, float* gb_acc,
-                     hipStream_t stream, void* fin_state = nullptr);
+void bn_act_backward_pre_dual(BnShape sh, const void* dz, const void* x, void* dx, const BnBwdStats& bs,
+                              BnPartials part, const void* x2, void* dx2, const BnBwdStats& bs2, float* ws2,
+                              hipStream_t stream);
+// dy2 (optional): a second upstream gradient of the same output, summed on load.
+// dres (optional): the residual branch's gradient (the gated, summed dy).
+void bn_act_backward(BnShape sh, const void* dy, const void* dy2, const uint8_t* mask, const void* x, void* dx,
+                     void* dres, const BnBwdStats& bs, float* ws, int relu, void* fin_state, hipStream_t stream);
 
 // BN (training) + ReLU + k x k / stride s / pad p max-pool, channels-last
-// [N, H, W, C] -> [N, OH, OW, C].  amax: one byte per OUTPUT element (window
-// position of the max, 0xff when the ReLU blocks the gradient).  The backward
-// gathers the pool gradient straight into the BN backward passes.
-// Requires N*H*W < 2^32.
+// [N, H, W, C] -> [N, OH, OW, C] (sh.M = N*H*W).  amax: one byte per OUTPUT
+// element (window position of the max, 0xff when the ReLU blocks the
+// gradient).  The backward gathers the pool gradient straight into the BN
+// backward passes.  Requires N*H*W < 2^32.  pre: as for bn_act_forward
+// (stem.hip / stem_f32.hip epilogues).
 struct PoolGeo {
   int H, W, OH, OW, k, s, p;
 };
-void bn_relu_pool_forward_pre(const void* x, void* y, uint8_t* amax, int64_t N, int C, PoolGeo pg, int elem_bytes,
-                              const float* psum,
-                              const float* psq, int gy, const float* w, const float* b, float eps, float momentum,
-                              float* run_mean, float* run_var, float* save_mean, float* save_invstd, float* scale,
-                              float* shift, int64_t* nbt, hipStream_t stream);
-void bn_relu_pool_forward(const void* x, void* y, uint8_t* amax, int64_t N, int C, PoolGeo pg, int elem_bytes,
-                          const float* w, const float* b, float eps, float momentum, float* run_mean, float* run_var,
-                          float* save_mean, float* save_invstd, float* scale, float* shift, float* ws, int64_t* nbt,
-                          hipStream_t stream);
-void bn_relu_pool_backward(const void* dy, const void* dy2, const uint8_t* amax, const void* x, void* dx, int64_t N,
-                           int C, PoolGeo pg, int elem_bytes, const float* w, const float* mean, const float* invstd,
-                           float* dgamma, float* dbeta, float* ws, float* gw_acc, float* gb_acc, hipStream_t stream);
+void bn_relu_pool_forward(BnShape sh, PoolGeo pg, const void* x, void* y, uint8_t* amax, const BnFwdStats& st,
+                          BnPartials pre, float* ws, hipStream_t stream);
+void bn_relu_pool_backward(BnShape sh, PoolGeo pg, const void* dy, const void* dy2, const uint8_t* amax,
+                           const void* x, void* dx, const BnBwdStats& bs, float* ws, hipStream_t stream);
 
 // ---------------------------------------------------------------------------
 // MFMA GEMMs and implicit-GEMM convolutions over channels-last activations
@@ -436,7 +431,7 @@ struct LazyArgs {
 };
 // stats (optional): [2][stats_rows][N] fp32 BatchNorm partials (sum, sum of
 // squares of the stored output) per workgroup row; returns the grid's row count
-// (the partial rows written, <= stats_rows) -- feed it to bn_act_forward_pre.
+// (the partial rows written, <= stats_rows) -- feed it to bn_act_forward as `pre`.
 // bias (optional): fp32 [N] added in the epilogue (before rounding and statistics)
 int gemm_nt(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int64_t M, int N, int K,
             bool f32, int cfg, int max_blocks, float* stats, int stats_rows, const float* bias, const BnBwdArgs* bn,
