@@ -15,8 +15,13 @@ and honoured inside the same kernels.  On the CPU, or for shapes the kernels
 do not take, it is ``F.scaled_dot_product_attention``.  Every block linear is
 a ``FastLinear`` (the FFN's first one with the GELU epilogue); the logits go
 through ``vocab_projection`` and the loss through ``xent.cross_entropy``.
-The pre-LN residual stream uses ``nn.LayerNorm`` (``add_layernorm`` returns
-only the normalised sum, which pre-LN cannot use).
+The pre-LN residual stream goes through ``ln.residual_layernorm``: each of
+the ``2 * layers + 1`` LayerNorms is one HIP row pass that adds the previous
+sub-layer's output (with its dropout) into the fp32 stream and returns the
+stream and its normalisation together, the latter in bf16 under autocast.
+``GPTForCausalLM.forward`` therefore carries ``(h, y)`` through
+``GPTBlock.attend`` / ``GPTBlock.mlp``; ``GPTBlock.forward`` is the same block
+on its own.
 """
 from __future__ import annotations
 
@@ -27,6 +32,7 @@ import torch.nn as nn
 
 from ..ops import attention, xent
 from ..ops.linear import FastLinear
+from ..ops.ln import residual_layernorm
 from .bert import vocab_projection
 
 
@@ -54,15 +60,23 @@ class GPTBlock(nn.Module):
         self.drop = nn.Dropout(c.dropout)
         self.p = c.dropout
 
-    def forward(self, x, attn_mask=None, key_mask=None):
-        """``key_mask``: a key-padding mask ([B, T] or packed bits) for the fused
+    def attend(self, y, attn_mask=None, key_mask=None):
+        """The attention sub-layer on the normalised stream ``y``, before its dropout and residual add.
+        ``key_mask``: a key-padding mask ([B, T] or packed bits) for the fused
         kernels; ``attn_mask`` (any SDPA mask) forces the SDPA path.  Both are
         combined with the causal mask."""
-        y = self.qkv(self.ln1(x))
-        a = attention.self_attention(y, self.heads, self.p, self.training, attn_mask=attn_mask, key_mask=key_mask,
-                                     causal=True)
-        x = x + self.drop(self.attn_out(a))
-        return x + self.drop(self.ffn_out(self.ffn_in(self.ln2(x), act="gelu")))
+        a = attention.self_attention(self.qkv(y), self.heads, self.p, self.training, attn_mask=attn_mask,
+                                     key_mask=key_mask, causal=True)
+        return self.attn_out(a)
+
+    def mlp(self, y):
+        """The feed-forward sub-layer on the normalised stream ``y``, before its dropout and residual add."""
+        return self.ffn_out(self.ffn_in(y, act="gelu"))
+
+    def forward(self, x, attn_mask=None, key_mask=None):
+        """The whole pre-LN block on the residual stream ``x`` (masks as in ``attend``)."""
+        x = x + self.drop(self.attend(self.ln1(x), attn_mask, key_mask))
+        return x + self.drop(self.mlp(self.ln2(x)))
 
 
 class GPTForCausalLM(nn.Module):
@@ -105,10 +119,15 @@ class GPTForCausalLM(nn.Module):
                 key_bits = attention.pack_key_mask(attention_mask)
             else:
                 mask = attention_mask[:, None, None, :].to(torch.bool)
-        for blk in self.blocks:
-            x = blk(x, mask, key_bits)
+        # every join adds a sub-layer's output into the stream h and normalises it for the next one
+        p, n = self.config.dropout, len(self.blocks)
+        h, y = residual_layernorm(None, x, self.blocks[0].ln1)
+        for i, blk in enumerate(self.blocks):
+            h, y = residual_layernorm(blk.attend(y, mask, key_bits), h, blk.ln2, p, self.training)
+            h, y = residual_layernorm(blk.mlp(y), h, self.blocks[i + 1].ln1 if i + 1 < n else self.ln_f, p,
+                                      self.training)
         # tied head: no bias
-        return vocab_projection(self.ln_f(x), self.word_embeddings.weight, None)
+        return vocab_projection(y, self.word_embeddings.weight, None)
 
 
 class CausalLMLoss(nn.Module):

@@ -58,6 +58,7 @@ HIP_SOURCES = [
     # gemm_inst_<family>.hip: one object per GEMM instantiation unit (-DGK_GEMM_UNIT=<n>, gemm_units.h)
     *["kernels/gemm_inst_%s.hip#%d" % (f, u) for u, f in enumerate(GEMM_UNIT_FAMILY)],
     "kernels/ln.hip",
+    "kernels/ln_pre.hip",
     "kernels/linear.hip",
     "kernels/lstm.hip",
     "kernels/stem.hip",
@@ -80,7 +81,9 @@ CXX_SOURCES = [
 # the GEMM units: no SLP vectorisation -- packed fp32 VALU (v_pk_add_f32) beside
 # MFMAs costs more issue cycles than scalar pairs (MI355X_MICROARCH.md constants);
 # measured on the bf16x6 split: GEMMs 2.5-4.5% faster (r5c20)
+# ln_pre.hip: no packed fp32 VALU ops (v_pk_*_f32) -- its row passes are bound by memory and gain nothing from them
 EXTRA_FLAGS = {"kernels/scatter.hip": ["-ffp-contract=off"],
+               "kernels/ln_pre.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                **{"kernels/gemm_inst_%s.hip" % f: ["-fno-slp-vectorize"] for f in set(GEMM_UNIT_FAMILY)}}
 
 

@@ -1641,6 +1641,63 @@ void add_ln_backward(at::Tensor dy, at::Tensor h, at::Tensor mean, at::Tensor rs
                       seed_word(seed_dev), cur_stream(h), dt == at::kFloat);
 }
 
+// the pre-LN join (ln_pre.hip): fp32 stream tensors (x, h, dh, dx), branch tensors (a, y, dy, da) bf16 or fp32
+const float* ln_vec(const at::Tensor& t, const char* name, int64_t n) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() >= n, name,
+              " must be a contiguous fp32 GPU tensor of ", n, " elements");
+  return t.data_ptr<float>();
+}
+
+void res_ln_forward(c10::optional<at::Tensor> a, at::Tensor x, at::Tensor gamma, at::Tensor beta, at::Tensor y,
+                    c10::optional<at::Tensor> h, at::Tensor mean, at::Tensor rstd, double eps, double p, int64_t seed,
+                    c10::optional<at::Tensor> seed_dev) {
+  TORCH_CHECK(x.dim() >= 1, "res_ln: x needs a row dimension");
+  const int64_t H = x.size(-1), R = H > 0 ? x.numel() / H : 0;
+  TORCH_CHECK(gk::add_ln_supported((int)H), "res_ln: unsupported hidden size");
+  const auto bt = y.scalar_type();
+  TORCH_CHECK(bt == at::kBFloat16 || bt == at::kFloat, "res_ln: bf16 or fp32 branch storage");
+  check_rows_ln(x, "res_ln x", R, H, at::kFloat);
+  check_rows_ln(y, "res_ln y", R, H, bt);
+  const bool has_a = a.has_value() && a->defined();
+  TORCH_CHECK(has_a == (h.has_value() && h->defined()), "res_ln: h is written exactly when a is given");
+  if (has_a) {
+    check_rows_ln(*a, "res_ln a", R, H, bt);
+    check_rows_ln(*h, "res_ln h", R, H, at::kFloat);
+  }
+  c10::DeviceGuard guard(x.device());
+  gk::res_ln_forward(has_a ? a->data_ptr() : nullptr, x.data_ptr<float>(), ln_vec(gamma, "gamma", H),
+                     ln_vec(beta, "beta", H), y.data_ptr(), has_a ? h->data_ptr<float>() : nullptr,
+                     const_cast<float*>(ln_vec(mean, "mean", R)), const_cast<float*>(ln_vec(rstd, "rstd", R)), R, (int)H,
+                     (float)eps, (float)p, (uint32_t)seed, seed_word(seed_dev), cur_stream(x), bt == at::kFloat);
+}
+
+void res_ln_backward(at::Tensor dy, at::Tensor h, at::Tensor mean, at::Tensor rstd, at::Tensor gamma,
+                     c10::optional<at::Tensor> dh, at::Tensor dx, c10::optional<at::Tensor> da,
+                     c10::optional<at::Tensor> dgamma, c10::optional<at::Tensor> dbeta, bool accumulate, at::Tensor ws,
+                     double p, int64_t seed, c10::optional<at::Tensor> seed_dev) {
+  TORCH_CHECK(h.dim() >= 1, "res_ln: h needs a row dimension");
+  const int64_t H = h.size(-1), R = H > 0 ? h.numel() / H : 0;
+  TORCH_CHECK(gk::add_ln_supported((int)H), "res_ln: unsupported hidden size");
+  const auto bt = dy.scalar_type();
+  TORCH_CHECK(bt == at::kBFloat16 || bt == at::kFloat, "res_ln: bf16 or fp32 branch storage");
+  check_rows_ln(dy, "res_ln dy", R, H, bt);
+  check_rows_ln(h, "res_ln h", R, H, at::kFloat);
+  check_rows_ln(dx, "res_ln dx", R, H, at::kFloat);
+  const bool has_dh = dh.has_value() && dh->defined(), has_da = da.has_value() && da->defined();
+  if (has_dh) check_rows_ln(*dh, "res_ln dh", R, H, at::kFloat);
+  if (has_da) check_rows_ln(*da, "res_ln da", R, H, bt);
+  ln_vec(ws, "ws", 2 * gk::add_ln_partial_rows(R) * H);
+  auto opt = [&](const c10::optional<at::Tensor>& t) -> float* {
+    return t.has_value() && t->defined() ? const_cast<float*>(ln_vec(*t, "dgamma / dbeta", H)) : nullptr;
+  };
+  c10::DeviceGuard guard(h.device());
+  gk::res_ln_backward(dy.data_ptr(), h.data_ptr<float>(), ln_vec(mean, "mean", R), ln_vec(rstd, "rstd", R),
+                      ln_vec(gamma, "gamma", H), has_dh ? dh->data_ptr<float>() : nullptr, dx.data_ptr<float>(),
+                      has_da ? da->data_ptr() : nullptr, opt(dgamma), opt(dbeta), accumulate ? 1 : 0,
+                      ws.data_ptr<float>(), R, (int)H, (float)p, (uint32_t)seed, seed_word(seed_dev), cur_stream(h),
+                      bt == at::kFloat);
+}
+
 // fused softmax cross-entropy (xent.hip)
 bool xent_supported(int64_t V) { return gk::xent_supported((int)V); }
 
@@ -2206,6 +2263,11 @@ TORCH_LIBRARY(gksgd, m) {
   m.def("add_ln_backward(Tensor dy, Tensor h, Tensor mean, Tensor rstd, Tensor? gamma, Tensor(a!) dx, "
         "Tensor(b!)? da, Tensor(c!)? dgamma, Tensor(d!)? dbeta, bool accumulate, Tensor(e!) ws, float p, int seed, "
         "Tensor? seed_dev=None) -> ()");
+  m.def("res_ln_forward(Tensor? a, Tensor x, Tensor gamma, Tensor beta, Tensor(a!) y, Tensor(b!)? h, "
+        "Tensor(c!) mean, Tensor(d!) rstd, float eps, float p, int seed, Tensor? seed_dev=None) -> ()");
+  m.def("res_ln_backward(Tensor dy, Tensor h, Tensor mean, Tensor rstd, Tensor gamma, Tensor? dh, Tensor(a!) dx, "
+        "Tensor(b!)? da, Tensor(c!)? dgamma, Tensor(d!)? dbeta, bool accumulate, Tensor(e!) ws, float p, int seed, "
+        "Tensor? seed_dev=None) -> ()");
   m.def("conv_tn_acc(Tensor dy, Tensor x, Tensor(a!) wout, Tensor zero, int stride, int pad, int cfg=0, int splits=0, "
         "Tensor? lz_x=None, Tensor? lz_coef=None, Tensor? lz_padz=None, Tensor? lz_padx=None) -> ()");
   m.def("colsum_acc(Tensor dy, Tensor(a!) db) -> ()");
@@ -2307,6 +2369,8 @@ TORCH_LIBRARY_IMPL(gksgd, CUDA, m) {
   m.impl("emb_forward", &emb_forward);
   m.impl("emb_backward", &emb_backward);
   m.impl("add_ln_backward", &add_ln_backward);
+  m.impl("res_ln_forward", &res_ln_forward);
+  m.impl("res_ln_backward", &res_ln_backward);
   m.impl("colsum_acc", &colsum_acc);
   m.impl("gelu_bwd_colsum", &gelu_bwd_colsum);
   m.impl("lstm_rec_gemm", &lstm_rec_gemm);

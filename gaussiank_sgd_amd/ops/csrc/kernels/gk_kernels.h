@@ -640,6 +640,20 @@ void add_ln_backward(const void* dy, const void* hsave, const float* mean, const
                      void* dx, void* da, float* dgamma, float* dbeta, int accumulate, float* ws, int64_t R, int H,
                      float p, uint32_t seed, const uint32_t* seed_dev, hipStream_t stream, bool f32 = false);
 
+// The pre-LN join (ln_pre.hip): the same pass returning both h and y.  The
+// residual stream x / h / dh / dx is fp32; the branch a / y / dy / da is bf16,
+// or fp32 with f32.  Same row rule, seed, mask and workspace as above.
+// forward : a null: the stream is x itself, h is not written (the first LN).
+// backward: dx = dLN/dh + dh (dh: the gradient arriving on h from downstream,
+//           null when nobody else consumed h), da = dx * mask / (1 - p) (null
+//           da: not written).
+void res_ln_forward(const void* a, const float* x, const float* gamma, const float* beta, void* y, float* h,
+                    float* mean, float* rstd, int64_t R, int H, float eps, float p, uint32_t seed,
+                    const uint32_t* seed_dev, hipStream_t stream, bool f32);
+void res_ln_backward(const void* dy, const float* h, const float* mean, const float* rstd, const float* gamma,
+                     const float* dh, float* dx, void* da, float* dgamma, float* dbeta, int accumulate, float* ws,
+                     int64_t R, int H, float p, uint32_t seed, const uint32_t* seed_dev, hipStream_t stream, bool f32);
+
 // ---------------------------------------------------------------------------
 // Linear-layer column passes over bf16 [M, N] row-major gradients (linear.hip);
 // N % 8 == 0, rows 16-byte aligned; db: fp32 [N], accumulated with float atomics.

@@ -17,65 +17,10 @@
 
 #include "common.h"
 #include "gk_kernels.h"
+#include "ln_common.h"
 
 namespace gk {
 namespace {
-
-constexpr int kLnMaxChunks = 8;          // per lane: H <= 64 * 8 * 8 = 4096
-constexpr int kLnRowsPerWave = 4;        // backward: rows per wave (RPW at a time)
-constexpr int kLnRowsPerBlock = kLnRowsPerWave * kWavesPerBlock;   // backward: one partial row per block
-
-__device__ __forceinline__ void load8(const uint16_t* p, float* v) {
-  const uint4 u = *reinterpret_cast<const uint4*>(p);
-  const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[2 * i] = __uint_as_float(w[i] << 16);
-    v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-  }
-}
-
-__device__ __forceinline__ void load8f(const float* p, float* v) {
-  const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-  v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-
-__device__ __forceinline__ uint32_t bf16r(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7f800000u) == 0x7f800000u && (u & 0x7fffffu)) return (u >> 16) | 0x40u;
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return u >> 16;
-}
-
-__device__ __forceinline__ void store8(uint16_t* p, const float* v) {
-  uint32_t w[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) w[i] = bf16r(v[2 * i]) | (bf16r(v[2 * i + 1]) << 16);
-  *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-// 8-element chunks of either storage type: 16 bytes of bf16 or 32 of fp32
-__device__ __forceinline__ void ld8(const uint16_t* p, float* v) { load8(p, v); }
-__device__ __forceinline__ void ld8(const float* p, float* v) { load8f(p, v); }
-__device__ __forceinline__ void st8(uint16_t* p, const float* v) { store8(p, v); }
-__device__ __forceinline__ void st8(float* p, const float* v) {
-  reinterpret_cast<float4*>(p)[0] = make_float4(v[0], v[1], v[2], v[3]);
-  reinterpret_cast<float4*>(p)[1] = make_float4(v[4], v[5], v[6], v[7]);
-}
-
-// keep element (row, col) with probability 1 - p: hash < keep threshold
-__device__ __forceinline__ bool keep(uint32_t seed, int64_t row, int col, uint32_t thr) {
-  return hash_u32((uint32_t)(row * 8191 + col), seed ^ (uint32_t)(row >> 19)) < thr;
-}
-
-// sum over the L lanes of one row (L = 64 / rows-per-wave, a power of two)
-template <int L>
-__device__ __forceinline__ float row_sum(float v) {
-#pragma unroll
-  for (int off = L / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // RPW rows per wave, L = 64 / RPW lanes per row; lane sl owns 16-byte chunks
 // sl + L j (j < CH) of its row.  BERT's H = 768 is 96 chunks: 2 rows per wave
@@ -310,20 +255,6 @@ __global__ __launch_bounds__(kBlock) void ln_param_finalize_kernel(const float* 
   if (dbeta) dbeta[col] = (accumulate ? dbeta[col] : 0.f) + (float)tb;
 }
 
-// (CH, RPW) for a row of nc 16-byte chunks: two rows per wave up to 256
-// chunks (H <= 2048), the fewest chunks per lane that cover the row
-template <template <int, int> class Launch>
-void ln_dispatch(int nc, Launch<1, 2> l12, Launch<2, 2> l22, Launch<3, 2> l32, Launch<4, 2> l42, Launch<6, 2> l62,
-                 Launch<8, 2> l82, Launch<8, 1> l81) {
-  if (nc <= 32) l12();
-  else if (nc <= 64) l22();
-  else if (nc <= 96) l32();
-  else if (nc <= 128) l42();
-  else if (nc <= 192) l62();
-  else if (nc <= 256) l82();
-  else l81();
-}
-
 }  // namespace
 
 bool add_ln_supported(int H) { return H % 8 == 0 && H >= 8 && H <= 64 * 8 * kLnMaxChunks; }
@@ -402,10 +333,18 @@ void add_ln_forward(const void* a, const void* x, const float* gamma, const floa
                     float* mean, float* rstd, int64_t R, int H, float eps, float p, uint32_t seed,
                     const uint32_t* seed_dev, hipStream_t stream, bool f32) {
   if (R <= 0) return;   // no rows: nothing to launch (a zero-sized grid is a launch error)
-  const uint32_t thr = p > 0.f ? (uint32_t)((1.0 - (double)p) * 4294967295.0) : 0u;
-  const float scale = p > 0.f ? 1.f / (1.f - p) : 1.f;
+  const uint32_t thr = ln_keep_threshold(p);
+  const float scale = ln_keep_scale(p);
   const LnFwdArgs args{a, x, gamma, beta, y, hsave, mean, rstd, R, H, eps, seed, thr, scale, seed_dev, stream, f32};
   ln_dispatch<LnFwdLaunch>(H >> 3, {&args}, {&args}, {&args}, {&args}, {&args}, {&args}, {&args});
+}
+
+void ln_param_reduce(const float* pg, const float* pb, int64_t P, int H, float* q, float* dgamma, float* dbeta,
+                     int accumulate, hipStream_t stream) {
+  hipLaunchKernelGGL(ln_param_partial_kernel, dim3((H + 63) / 64, kFinSplits), dim3(kBlock), 0, stream, pg, pb, P, H,
+                     q);
+  hipLaunchKernelGGL(ln_param_finalize_kernel, dim3((H + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, q, H,
+                     dgamma, dbeta, accumulate);
 }
 
 void add_ln_backward(const void* dy, const void* hsave, const float* mean, const float* rstd, const float* gamma,
@@ -418,20 +357,15 @@ void add_ln_backward(const void* dy, const void* hsave, const float* mean, const
     }
     return;
   }
-  const uint32_t thr = p > 0.f ? (uint32_t)((1.0 - (double)p) * 4294967295.0) : 0u;
-  const float scale = p > 0.f ? 1.f / (1.f - p) : 1.f;
+  const uint32_t thr = ln_keep_threshold(p);
+  const float scale = ln_keep_scale(p);
   const int64_t P = (R + kLnRowsPerBlock - 1) / kLnRowsPerBlock;
   float* pg = ws;
   float* pb = ws + P * H;
   float* q = ws + 2 * P * H;   // [2][kFinSplits][H]: fits the 2 * add_ln_partial_rows(R) * H of the workspace
   const LnBwdArgs args{dy, hsave, mean, rstd, gamma, dx, da, pg, pb, R, H, seed, thr, scale, seed_dev, stream, f32};
   ln_dispatch<LnBwdLaunch>(H >> 3, {&args}, {&args}, {&args}, {&args}, {&args}, {&args}, {&args});
-  if (dgamma || dbeta) {
-    hipLaunchKernelGGL(ln_param_partial_kernel, dim3((H + 63) / 64, kFinSplits), dim3(kBlock), 0, stream, pg, pb, P, H,
-                       q);
-    hipLaunchKernelGGL(ln_param_finalize_kernel, dim3((H + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, q, H,
-                       dgamma, dbeta, accumulate);
-  }
+  if (dgamma || dbeta) ln_param_reduce(pg, pb, P, H, q, dgamma, dbeta, accumulate, stream);
 }
 
 }  // namespace gk

@@ -11,6 +11,15 @@ length the kernels do not take) it is the plain PyTorch composition with
 identical semantics; bf16 rows through fp32 parameters outside autocast are
 normalised in fp32 and returned in bf16 there, as the kernels do.  ``ln`` is an ordinary
 ``nn.LayerNorm`` (its parameters / state_dict keys are untouched).
+
+``residual_layernorm(a, x, ln, p)`` is the pre-LN join (``csrc/kernels/
+ln_pre.hip``): it returns both the new residual stream ``h = x +
+dropout_p(a)`` and ``ln(h)`` from one row pass.  The stream stays fp32 over
+all of a decoder's joins; the branch tensors (``a`` in, ``ln(h)`` out and
+their gradients) are bf16 under autocast, so the fp32 LayerNorm that autocast
+forces and the cast back in front of the next linear are gone.  The backward
+takes the gradient that arrives on ``h`` from downstream inside the same
+pass.  ``GKSGD_PRELN_FUSED=0`` keeps the PyTorch composition.
 """
 from __future__ import annotations
 
@@ -114,3 +123,89 @@ def add_layernorm(a: torch.Tensor, x: torch.Tensor, ln: nn.LayerNorm, p: float =
         # as the kernels do, and keep the rows' dtype
         return F.layer_norm(h.to(ln.weight.dtype), ln.normalized_shape, ln.weight, ln.bias, ln.eps).to(h.dtype)
     return ln(h)
+
+
+class _ResLNFn(torch.autograd.Function):
+    """(h, y) = (x + dropout_p(a), LN(h)); ``a`` None: h is not produced (the stream is x)."""
+
+    @staticmethod
+    def forward(ctx, a, x, gamma, beta, eps, p, seed, direct, seed_dev, cd):
+        # direct, seed_dev: as in _AddLNFn; cd: storage dtype of the branch tensors (a, y, dy, da)
+        ctx.set_materialize_grads(False)
+        H = x.shape[-1]
+        x = x.contiguous()
+        R = x.numel() // H
+        if a is not None:
+            a = a.to(cd).contiguous()
+        h = torch.empty_like(x) if a is not None else None
+        y = torch.empty(x.shape, dtype=cd, device=x.device)
+        mean = torch.empty(R, dtype=torch.float32, device=x.device)
+        rstd = torch.empty(R, dtype=torch.float32, device=x.device)
+        g = gamma.detach().float().contiguous()
+        _ops().res_ln_forward(a, x, g, beta.detach().float().contiguous(), y, h, mean, rstd, float(eps), float(p),
+                              int(seed), seed_dev)
+        ctx.save_for_backward(x if a is None else h, mean, rstd, g)
+        ctx.p, ctx.seed, ctx.seed_dev = float(p), int(seed), seed_dev
+        ctx.has_a, ctx.cd, ctx.gdtype, ctx.direct = a is not None, cd, gamma.dtype, direct
+        return h, y
+
+    @staticmethod
+    def backward(ctx, dh, dy):
+        # dh: what the rest of the model did with the stream h (None for the last join: a null pointer);
+        # dy None (only h was used): zeros, so that dx = dh and da is its masked copy
+        h, mean, rstd, g = ctx.saved_tensors
+        H = h.shape[-1]
+        R = h.numel() // H
+        dy = torch.zeros(h.shape, dtype=ctx.cd, device=h.device) if dy is None else dy.to(ctx.cd).contiguous()
+        if dh is not None:
+            dh = dh.float().contiguous()
+        dx = torch.empty_like(h)
+        # fp32 branch without dropout: da is dx itself, as in _AddLNFn
+        own_da = ctx.has_a and ctx.needs_input_grad[0] and (ctx.p > 0 or ctx.cd != torch.float32)
+        da = torch.empty(h.shape, dtype=ctx.cd, device=h.device) if own_da else None
+        direct = ctx.direct
+        if direct is not None:
+            dg, db = direct
+        else:
+            dg = torch.empty(H, dtype=torch.float32, device=h.device) if ctx.needs_input_grad[2] else None
+            db = torch.empty(H, dtype=torch.float32, device=h.device) if ctx.needs_input_grad[3] else None
+        ws = torch.empty(int(_ops().add_ln_ws_floats(R, H)), dtype=torch.float32, device=h.device)
+        _ops().res_ln_backward(dy, h, mean, rstd, g, dh, dx, da, dg, db, direct is not None, ws, ctx.p, ctx.seed,
+                               ctx.seed_dev)
+        if ctx.has_a and da is None:
+            da = dx
+        if direct is not None:
+            dg = db = None
+        return (da, dx, dg.to(ctx.gdtype) if dg is not None else None,
+                db.to(ctx.gdtype) if db is not None else None, None, None, None, None, None, None)
+
+
+def _branch_dtype(a, x: torch.Tensor):
+    """Storage dtype of the join's branch tensors, resolved as in ``_compute_dtype`` (None: composition)."""
+    dev = x.device.type
+    autocast = torch.is_autocast_enabled(dev)
+    if (a is not None and a.dtype == torch.bfloat16) or (autocast and torch.get_autocast_dtype(dev) == torch.bfloat16):
+        return torch.bfloat16
+    if (a is None or a.dtype == torch.float32) and not autocast and os.environ.get("GKSGD_LN_F32", "1") != "0":
+        return torch.float32
+    return None
+
+
+def residual_layernorm(a, x: torch.Tensor, ln: nn.LayerNorm, p: float = 0.0, training: bool = True):
+    """The pre-LN join: ``h = x + dropout_p(a)`` (``a`` None: ``h`` is ``x``) and ``ln(h)``, as ``(h, y)``."""
+    if (x.is_cuda and x.dtype == torch.float32 and (a is None or a.shape == x.shape) and
+            ln.elementwise_affine and ln.bias is not None and len(ln.normalized_shape) == 1 and
+            os.environ.get("GKSGD_PRELN_FUSED", "1") != "0"):
+        cd = _branch_dtype(a, x)
+        if cd is not None and load() and bool(_ops().add_ln_supported(x.shape[-1])):
+            pk = float(p) if training and a is not None else 0.0
+            seed = int(torch.randint(0, 2 ** 31 - 1, (1,), generator=seed_generator())) if pk > 0 else 0
+            direct = getattr(ln, "_gk_direct", None)
+            if direct is not None and not (torch.is_grad_enabled() and ln.weight.requires_grad and
+                                           ln.bias.requires_grad):
+                direct = None
+            h, y = _ResLNFn.apply(a, x, ln.weight, ln.bias, ln.eps, pk, seed, direct,
+                                  capture_seed_word(x.device) if pk > 0 else None, cd)
+            return (x if a is None else h), y
+    h = x if a is None else x + F.dropout(a, p, training)
+    return h, ln(h)

@@ -144,7 +144,7 @@ def install_bf16_shadow(model: nn.Module, opt) -> int:
             if table:
                 mod._gk_shadow = table
         elif isinstance(mod, nn.LayerNorm) and mod.elementwise_affine and mod.bias is not None:
-            # ops/ln.py add_layernorm: the fused backward accumulates dgamma /
+            # ops/ln.py add_layernorm / residual_layernorm: the fused backward accumulates dgamma /
             # dbeta straight into the arena (plain ln(x) calls ignore this)
             if mod.weight in names and mod.bias in names:
                 mod._gk_direct = (arena.grad_views[names[mod.weight]], arena.grad_views[names[mod.bias]])
