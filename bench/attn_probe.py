@@ -3,7 +3,7 @@
 times per call and the achieved MFMA rate (fwd 4*B*H*T^2*d FLOPs, bwd 2.5x).
 
     python bench/attn_probe.py [--B 32] [--T 512] [--heads 12] [--p 0.1] [--dtype bf16|fp32] [--pad] [--causal]
-                                 [--iters 20]
+                                 [--docs N[,N..]] [--iters 20]
 
 --pad: a key-padding mask with per-sequence valid lengths drawn uniformly from
 [T/4, T] (fixed seed).  Times ours with the mask ("ours_masked") against SDPA
@@ -20,6 +20,15 @@ tile model: per (batch, head) the forward and dQ kernels visit nqb (nqb + 1) of
 2 nqb^2 key tiles and the dK/dV kernel as many query tiles, nqb = T / 128
 (0.625 at T = 512, 0.5625 at T = 1024).  The TFLOP/s of causal rows count the
 dense op's FLOPs.
+
+--docs N[,N..] (with --causal): every sequence split into N documents at seeded
+random boundaries (packed rows).  Per N: ours with the document mask
+("ours_docsN", the DOC kernels) and SDPA with the block-diagonal causal mask
+("sdpa_docsN"); "docs" holds their time ratios to the causal row timed last
+("ours_causal_again": the first row of a process runs before the clocks settle
+and reads 10-18% slow) and to each other, and the tile model counted from the layout: key tiles the forward / dQ
+kernels visit and query tiles the dK/dV kernel visits, over the causal counts.
+"ours_causal_again" times the causal row once more after the document rows.
 """
 import argparse
 import json
@@ -55,6 +64,7 @@ def main():
     ap.add_argument("--dtype", choices=["bf16", "fp32"], default="bf16")
     ap.add_argument("--pad", action="store_true", help="key-padding mask, valid lengths uniform in [T/4, T]")
     ap.add_argument("--causal", action="store_true", help="causal=True against the same shape without it")
+    ap.add_argument("--docs", default="", help="with --causal: documents per sequence, comma-separated")
     ap.add_argument("--iters", type=int, default=20, help="timed calls per row (after iters / 4 warm-up calls)")
     ap.add_argument("--only", default="", help="comma-separated rows to time (default: all)")
     ap.add_argument("--json-out", default="")
@@ -99,6 +109,25 @@ def main():
             rows += [("ours_causal_masked", *pair(lambda: fn.apply(qkv, Hh, p, 1, None, bits, True))),
                      ("sdpa_causal_masked", *pair(lambda: attention._sdpa(qkv, Hh, p, bmask, True)))]
 
+    docs = [int(n) for n in a.docs.split(",") if n]
+    assert a.causal or not docs, "--docs needs --causal"
+    tiles = {}
+    for n in docs:
+        g = torch.Generator().manual_seed(4321 + n)
+        cuts = torch.stack([torch.randperm(T - 1, generator=g)[:n - 1] + 1 for _ in range(B)])   # n - 1 boundaries
+        ids = torch.zeros(B, T + 1, dtype=torch.int64).scatter_(1, cuts, 1)[:, :T].cumsum(1).cuda()
+        seg = attention.pack_segments(ids)
+        dmask = attention.segments_visible(seg)[:, None]
+        # tiles visited per layout over the causal count: forward / dQ from start[128 qb], dK/dV to end[128 kb + 127]
+        nqb, st, en = T // 128, seg[:, 0, ::128].cpu() // 64, seg[:, 1, 127::128].cpu() // 64 + 1
+        qb = torch.arange(nqb)
+        tiles[n] = {"fwd": round(float((2 * qb + 2 - st).sum()) / float(B * (2 * qb + 2).sum()), 4),
+                    "bwd_kv": round(float((en - 2 * qb).sum()) / float(B * (T // 64 - 2 * qb).sum()), 4)}
+        rows += [("ours_docs%d" % n, *pair(lambda seg=seg: fn.apply(qkv, Hh, p, 1, None, None, True, seg))),
+                 ("sdpa_docs%d" % n, *pair(lambda dmask=dmask: attention._sdpa(qkv, Hh, p, dmask)))]
+    if docs:
+        rows += [("ours_causal_again", *pair(lambda: fn.apply(qkv, Hh, p, 1, None, None, True)))]
+
     only = set(filter(None, a.only.split(",")))
     for name, f, fb in rows:
         if only and name not in only:
@@ -113,6 +142,12 @@ def main():
         for c, d in (("ours_causal", "ours"), ("ours_causal_masked", "ours_masked")):
             if c in res and d in res:
                 res["causal"][c + "/" + d] = {k: round(res[c][k + "_us"] / res[d][k + "_us"], 4) for k in ("fwd", "bwd")}
+    for n in docs:
+        o, c, sd = res.get("ours_docs%d" % n), res.get("ours_causal_again"), res.get("sdpa_docs%d" % n)
+        res.setdefault("docs", {})[str(n)] = d = {"tile_model": tiles[n]}
+        for name, num, den in (("ours_docs/ours_causal", o, c), ("ours_docs/sdpa_docs", o, sd)):
+            if num and den:
+                d[name] = {k: round(num[k + "_us"] / den[k + "_us"], 4) for k in ("fwd", "bwd", "fwd_bwd")}
     print(json.dumps(res))
     if a.json_out:
         with open(a.json_out, "w") as fh:

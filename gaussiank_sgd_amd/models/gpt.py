@@ -11,7 +11,11 @@ On the GPU, attention is the flash-style HIP kernel of ops/attention.py with
 ``causal=True`` on the packed QKV projection: no [T, T] mask or score matrix,
 no head split / merge copies, and the key tiles above the diagonal are never
 visited.  ``attention_mask`` (key padding) is packed to bits once per forward
-and honoured inside the same kernels.  On the CPU, or for shapes the kernels
+and honoured inside the same kernels.  ``doc_ids`` ([B, T]) marks the documents
+of packed rows: they are packed once per forward (``attention.pack_segments``)
+and every block's attention takes them (the kernels' document variant), and
+positions restart at each document, so a packed document gets the logits it
+would get alone in a row.  On the CPU, or for shapes the kernels
 do not take, it is ``F.scaled_dot_product_attention``.  Every block linear is
 a ``FastLinear`` (the FFN's first one with the GELU epilogue); the logits go
 through ``vocab_projection`` and the loss through ``xent.cross_entropy``.
@@ -60,22 +64,23 @@ class GPTBlock(nn.Module):
         self.drop = nn.Dropout(c.dropout)
         self.p = c.dropout
 
-    def attend(self, y, attn_mask=None, key_mask=None):
+    def attend(self, y, attn_mask=None, key_mask=None, segments=None):
         """The attention sub-layer on the normalised stream ``y``, before its dropout and residual add.
         ``key_mask``: a key-padding mask ([B, T] or packed bits) for the fused
         kernels; ``attn_mask`` (any SDPA mask) forces the SDPA path.  Both are
-        combined with the causal mask."""
+        combined with the causal mask, and with the documents of ``segments``
+        (document ids or ``attention.pack_segments``)."""
         a = attention.self_attention(self.qkv(y), self.heads, self.p, self.training, attn_mask=attn_mask,
-                                     key_mask=key_mask, causal=True)
+                                     key_mask=key_mask, causal=True, segments=segments)
         return self.attn_out(a)
 
     def mlp(self, y):
         """The feed-forward sub-layer on the normalised stream ``y``, before its dropout and residual add."""
         return self.ffn_out(self.ffn_in(y, act="gelu"))
 
-    def forward(self, x, attn_mask=None, key_mask=None):
+    def forward(self, x, attn_mask=None, key_mask=None, segments=None):
         """The whole pre-LN block on the residual stream ``x`` (masks as in ``attend``)."""
-        x = x + self.drop(self.attend(self.ln1(x), attn_mask, key_mask))
+        x = x + self.drop(self.attend(self.ln1(x), attn_mask, key_mask, segments))
         return x + self.drop(self.mlp(self.ln2(x)))
 
 
@@ -104,13 +109,19 @@ class GPTForCausalLM(nn.Module):
         if isinstance(m, nn.Linear) and m.bias is not None:
             nn.init.zeros_(m.bias)
 
-    def forward(self, input_ids, attention_mask=None):
+    def forward(self, input_ids, attention_mask=None, doc_ids=None):
         """Next-token logits [B, T, V].  ``attention_mask``: [B, T] key padding
-        (nonzero = real token), on top of the causal mask."""
+        (nonzero = real token), on top of the causal mask.  ``doc_ids``: [B, T]
+        integer document ids of packed rows (a boundary wherever neighbours
+        differ): a token sees its own document only and positions restart."""
         B, T = input_ids.shape
         if T > self.config.max_position:
             raise ValueError("sequence length %d exceeds max_position %d" % (T, self.config.max_position))
         pos = torch.arange(T, device=input_ids.device)
+        segments = None
+        if doc_ids is not None:
+            segments = attention.pack_segments(doc_ids)   # once, shared by every block
+            pos = pos - segments[:, 0]                    # [B, T]: t - start[t]
         x = self.emb_drop(self.word_embeddings(input_ids) + self.position_embeddings(pos))
         mask = key_bits = None
         if attention_mask is not None:
@@ -123,7 +134,7 @@ class GPTForCausalLM(nn.Module):
         p, n = self.config.dropout, len(self.blocks)
         h, y = residual_layernorm(None, x, self.blocks[0].ln1)
         for i, blk in enumerate(self.blocks):
-            h, y = residual_layernorm(blk.attend(y, mask, key_bits), h, blk.ln2, p, self.training)
+            h, y = residual_layernorm(blk.attend(y, mask, key_bits, segments), h, blk.ln2, p, self.training)
             h, y = residual_layernorm(blk.mlp(y), h, self.blocks[i + 1].ln1 if i + 1 < n else self.ln_f, p,
                                       self.training)
         # tied head: no bias

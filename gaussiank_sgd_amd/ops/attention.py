@@ -33,9 +33,23 @@ over keys ``0 .. q``) gives output 0, zero dQ and adds nothing to dK / dV, where
 SDPA gives NaN.  The causal bf16 forward keeps ``out_lo`` too, with or without
 a key mask: the first rows of a sequence see few keys.
 
+``segments`` (with ``causal=True`` only) is the document mask of packed
+sequences: several documents laid end to end in one row, every token seeing
+the earlier tokens of its own document only.  It is ``[B, T]`` document ids (a
+boundary wherever two neighbours differ) or the packed form of
+``pack_segments``: int32 ``[B, 2, T]``, the index of the first and of the last
+token of each token's document.  Query ``q`` sees key ``k`` iff
+``start[q] <= k <= q``, ANDed with ``key_mask``.  The kernels take it as the
+DOC variant of the causal instantiations: a row block starts at the key tile
+of its first row's document (the dK/dV kernel stops at the query tile where
+its last key's document ends), a wave skips the arithmetic of tiles wholly in
+other documents, and only tiles that hold a boundary are masked element by
+element.  The tensor is data, not a captured constant: a replayed graph reads
+the layout its buffer holds then.  Measured (profiles/attn_docs_probe.txt).
+
 Elsewhere (CPU, ``attn_mask``, other head dims) it is
 ``F.scaled_dot_product_attention`` with identical semantics (``is_causal``, or
-the lower triangle merged into the mask).
+the lower triangle and the documents merged into the mask).
 
 Not in the reference (its model zoo has no transformer); BASELINE config 5
 (BERT-base MLM) runs it.
@@ -136,25 +150,71 @@ def merge_masks(attn_mask, key_mask, B: int, T: int):
     return attn_mask.masked_fill(~km, float("-inf"))
 
 
+def pack_segments(doc_ids: torch.Tensor) -> torch.Tensor:
+    """``[B, T]`` integer document ids -> int32 ``[B, 2, T]``: ``[:, 0, t]`` / ``[:, 1, t]`` is the index of the
+    first / last token of ``t``'s document.  A document is a run of equal neighbouring ids.  Torch expressions on
+    either device and no host read, so it records into a captured step."""
+    if doc_ids.dim() != 2 or doc_ids.is_floating_point():
+        raise ValueError("doc_ids must be integer [B, T], got %s %s" % (tuple(doc_ids.shape), doc_ids.dtype))
+    B, T = doc_ids.shape
+    idx = torch.arange(T, device=doc_ids.device).expand(B, T)
+    cut = doc_ids[:, 1:] != doc_ids[:, :-1]                     # a boundary between t and t + 1
+    edge = torch.ones(B, 1, dtype=torch.bool, device=doc_ids.device)
+    first = torch.cat([edge, cut], 1)    # t opens a document
+    last = torch.cat([cut, edge], 1)     # t closes one
+    start = torch.where(first, idx, idx.new_zeros(())).cummax(1).values
+    end = torch.where(last, idx, idx.new_full((), T - 1)).flip(1).cummin(1).values.flip(1)
+    return torch.stack([start, end], 1).to(torch.int32).contiguous()
+
+
+def _is_packed_segments(segments: torch.Tensor, B: int, T: int) -> bool:
+    """The packed int32 [B, 2, T] form, as opposed to [B, T] document ids (shape tells)."""
+    if segments.dim() == 3 and tuple(segments.shape) == (B, 2, T):
+        return True
+    if tuple(segments.shape) != (B, T):
+        raise ValueError("segments must be [B, T] = [%d, %d] document ids or packed int32 [B, 2, T], got %s %s"
+                         % (B, T, tuple(segments.shape), segments.dtype))
+    return False
+
+
+def _segments(segments: torch.Tensor, B: int, T: int) -> torch.Tensor:
+    if _is_packed_segments(segments, B, T):
+        return segments.to(torch.int32).contiguous()
+    return pack_segments(segments)
+
+
+def segments_visible(segments: torch.Tensor) -> torch.Tensor:
+    """Packed segments ``[B, 2, T]`` -> bool ``[B, T, T]``, True where query (row) sees key (column):
+    ``start[q] <= k <= q``."""
+    T = segments.shape[-1]
+    k = torch.arange(T, device=segments.device)
+    return (k[None, None, :] >= segments[:, 0, :, None]) & (k[None, None, :] <= k[None, :, None])
+
+
 def causal_mask(T: int, device) -> torch.Tensor:
     """bool ``[T, T]``, True where query (row) sees key (column): ``k <= q``."""
     return torch.ones(T, T, dtype=torch.bool, device=device).tril_()
 
 
 def reference_attention(qkv: torch.Tensor, heads: int, p: float = 0.0, seed: int = 0,
-                        key_mask=None, causal: bool = False) -> torch.Tensor:
-    """fp32 composition with the kernels' exact dropout mask (autograd-able);
+                        key_mask=None, causal: bool = False, segments=None) -> torch.Tensor:
+    """fp32 composition (fp64 for fp64 input) with the kernels' exact dropout mask (autograd-able);
     ``key_mask``: masked keys score -inf; ``causal``: so do keys after the
-    query.  A row without a visible valid key gives zeros, not NaN."""
+    query; ``segments`` (either form, with ``causal``): and keys of earlier
+    documents.  A row without a visible valid key gives zeros, not NaN."""
+    if segments is not None and not causal:
+        raise ValueError("segments need causal=True")
     B, T, H3 = qkv.shape
     d = H3 // (3 * heads)
-    x = qkv.float().view(B, T, 3, heads, d)
+    x = (qkv if qkv.dtype == torch.float64 else qkv.float()).view(B, T, 3, heads, d)
     q, k, v = (x[:, :, i].transpose(1, 2) for i in range(3))
     s = torch.matmul(q, k.transpose(-1, -2)) / d ** 0.5
     if key_mask is not None:
         s = s.masked_fill(~key_mask_bool(key_mask, B, T)[:, None, None, :], float("-inf"))
     if causal:
         s = s.masked_fill(~causal_mask(T, s.device), float("-inf"))
+        if segments is not None:
+            s = s.masked_fill(~segments_visible(_segments(segments, B, T))[:, None], float("-inf"))
         if key_mask is not None:
             # rows that see nothing: a finite score row (so that softmax and its gradient stay finite), zeroed after
             dark = torch.isinf(s).all(dim=-1, keepdim=True)
@@ -176,30 +236,31 @@ def _flash_attn_fn(name: str, dtype, fwd: str, bwd: str, keep_lo: bool):
     delta = rowsum(dO * O) nearly cancel, so the bf16 forward also keeps what the rounding of O dropped
     (``out_lo``; causal: the first rows of a sequence are such rows) and both ops take it."""
 
-    def forward(ctx, qkv, heads, p, seed, seed_dev=None, key_bits=None, causal=False):
+    def forward(ctx, qkv, heads, p, seed, seed_dev=None, key_bits=None, causal=False, segments=None):
         # seed_dev: the graph replay word (ops.graph_seed_word) under capture --
         # forward and backward of one replay read the same word
         # key_bits: the packed key mask (pack_key_mask), shared with the backward
         # causal: a Python bool, it picks the kernels' CAUSAL instantiations
+        # segments: the packed documents (pack_segments), shared with the backward; they pick the DOC ones
         B, T, _ = qkv.shape
         out = torch.empty(B, T, heads * HEAD_DIM, dtype=dtype, device=qkv.device)
         lse = torch.empty(B * heads * T, dtype=torch.float32, device=qkv.device)
         lo = (None if key_bits is None and not causal else torch.empty_like(out),) if keep_lo else ()
         getattr(_ops(), fwd)(qkv, out, lse, int(heads), float(p), int(seed), seed_dev, key_bits, *lo,
-                             bool(causal))
-        ctx.save_for_backward(qkv, out, lse, key_bits, *lo)
+                             bool(causal), segments)
+        ctx.save_for_backward(qkv, out, lse, key_bits, segments, *lo)
         ctx.heads, ctx.p, ctx.seed, ctx.seed_dev = int(heads), float(p), int(seed), seed_dev
         ctx.causal = bool(causal)
         return out
 
     def backward(ctx, dout):
-        qkv, out, lse, key_bits, *lo = ctx.saved_tensors
+        qkv, out, lse, key_bits, segments, *lo = ctx.saved_tensors
         dout = dout.to(dtype).contiguous()
         delta = torch.empty_like(lse)
         dqkv = torch.empty_like(qkv)
         getattr(_ops(), bwd)(qkv, out, dout, lse, delta, dqkv, ctx.heads, ctx.p, ctx.seed, ctx.seed_dev, key_bits,
-                             *lo, ctx.causal)
-        return dqkv, None, None, None, None, None, None
+                             *lo, ctx.causal, segments)
+        return dqkv, None, None, None, None, None, None, None
 
     # the class statement's own call, so that the class and its autograd node carry ``name``
     return type(torch.autograd.Function)(name, (torch.autograd.Function,),
@@ -268,9 +329,31 @@ def _sdpa(qkv: torch.Tensor, heads: int, p: float, attn_mask=None, causal: bool 
     return o.transpose(1, 2).reshape(B, T, heads * d)
 
 
+def _sdpa_segments(qkv: torch.Tensor, heads: int, p: float, mask, segments: torch.Tensor) -> torch.Tensor:
+    """The SDPA path under a document mask (``segments`` packed): the documents' visibility -- the lower
+    triangle included -- merged into ``mask``.  A query without a visible key (a key mask can leave one) gives
+    zeros as in the kernels: such a row gets a finite score row and its output is zeroed."""
+    B, T = qkv.shape[0], qkv.shape[1]
+    vis = segments_visible(segments)[:, None]
+    if mask is not None and mask.dtype == torch.bool:
+        vis = vis & mask
+    dark = ~vis.any(-1, keepdim=True)
+    full = vis | dark
+    if mask is not None and mask.dtype != torch.bool:
+        full = torch.where(full, mask, mask.new_full((), float("-inf")))
+    o = _sdpa(qkv, heads, p, full)
+    # [B, 1 or heads, T, 1] -> rows of the merged-heads output
+    dark = dark.expand(B, heads, T, 1).transpose(1, 2).reshape(B, T, heads, 1)
+    return o.view(B, T, heads, -1).masked_fill(dark, 0.0).view(B, T, -1)
+
+
 def self_attention(qkv: torch.Tensor, heads: int, p: float = 0.0, training: bool = True,
-                   attn_mask=None, seed: int = None, key_mask=None, causal: bool = False) -> torch.Tensor:
+                   attn_mask=None, seed: int = None, key_mask=None, causal: bool = False,
+                   segments=None) -> torch.Tensor:
     """``[B, T, 3*heads*d]`` packed projection -> ``[B, T, heads*d]`` attention output.
+    ``segments`` (needs ``causal=True``): the documents of packed sequences,
+    ``[B, T]`` ids or packed (``pack_segments``); a query sees its own document
+    only.  The fused kernels take it; on the SDPA path it is merged into the mask.
     ``causal``: query ``q`` sees keys ``k <= q`` only (ANDed with ``key_mask``);
     the fused kernels take it (and then keep ``out_lo``, as with a key mask).  On
     the SDPA path a query without a visible valid key gives NaN, in the kernels 0.
@@ -282,12 +365,20 @@ def self_attention(qkv: torch.Tensor, heads: int, p: float = 0.0, training: bool
     more bf16 [B, T, heads*d] activation kept per call)."""
     p = float(p) if training else 0.0
     B, T = qkv.shape[0], qkv.shape[1]
+    if segments is not None:
+        if not causal:
+            raise ValueError("segments need causal=True: a document mask is a variant of the causal mask")
+        segments = _segments(segments, B, T)   # packed once, kept for the backward
     if attn_mask is None and fused_available(qkv, heads):
         if seed is None:
             seed = int(torch.randint(0, 2 ** 31 - 1, (1,), generator=seed_generator())) if p > 0 else 0
         seed_dev = capture_seed_word(qkv.device) if p > 0 else None
         bits = None if key_mask is None else _key_bits(key_mask, B, T)   # packed once, kept for the backward
+        tail = (bool(causal),) if segments is None else (True, segments)
         if _compute_dtype(qkv) == torch.float32:
-            return _FlashAttnF32Fn.apply(qkv.contiguous(), heads, p, seed, seed_dev, bits, bool(causal))
-        return _FlashAttnFn.apply(qkv.to(torch.bfloat16).contiguous(), heads, p, seed, seed_dev, bits, bool(causal))
-    return _sdpa(qkv, heads, p, merge_masks(attn_mask, key_mask, B, T), bool(causal))
+            return _FlashAttnF32Fn.apply(qkv.contiguous(), heads, p, seed, seed_dev, bits, *tail)
+        return _FlashAttnFn.apply(qkv.to(torch.bfloat16).contiguous(), heads, p, seed, seed_dev, bits, *tail)
+    mask = merge_masks(attn_mask, key_mask, B, T)
+    if segments is None:
+        return _sdpa(qkv, heads, p, mask, bool(causal))
+    return _sdpa_segments(qkv, heads, p, mask, segments)

@@ -1822,6 +1822,17 @@ const uint32_t* key_bits_ptr(const c10::optional<at::Tensor>& t, const at::Tenso
   return reinterpret_cast<const uint32_t*>(t->data_ptr<int32_t>());
 }
 
+// documents of packed sequences: int32 [B, 2, T] (first / last token of each token's document) on qkv's
+// device, with causal only (kernels/attn_common.h); null when absent
+const int32_t* segments_ptr(const c10::optional<at::Tensor>& t, const at::Tensor& qkv, bool causal) {
+  if (!t.has_value() || !t->defined()) return nullptr;
+  TORCH_CHECK(causal, "segments need causal=True (the document mask is a variant of the causal kernels)");
+  TORCH_CHECK(t->is_cuda() && t->device() == qkv.device() && t->scalar_type() == at::kInt && t->is_contiguous() &&
+                  t->dim() == 3 && t->size(0) == qkv.size(0) && t->size(1) == 2 && t->size(2) == qkv.size(1),
+              "segments must be a contiguous int32 [B, 2, T] tensor on qkv's device");
+  return t->data_ptr<int32_t>();
+}
+
 // the output's rounding residue (bf16, with key_bits or causal only); null when absent
 void* out_lo_ptr(const c10::optional<at::Tensor>& t, const uint32_t* key_bits, bool causal, int64_t rows,
                  int64_t cols) {
@@ -1862,41 +1873,48 @@ AttnCall check_attn_call(at::ScalarType dt, const at::Tensor& qkv, const at::Ten
 
 void attn_fwd(at::Tensor qkv, at::Tensor out, at::Tensor lse, int64_t heads, double p, int64_t seed,
               c10::optional<at::Tensor> seed_dev, c10::optional<at::Tensor> key_bits,
-              c10::optional<at::Tensor> out_lo, bool causal) {
+              c10::optional<at::Tensor> out_lo, bool causal, c10::optional<at::Tensor> segments) {
   const AttnCall c = check_attn_call(at::kBFloat16, qkv, out, lse, heads, p, key_bits);
   void* lo = out_lo_ptr(out_lo, c.key_bits, causal, c.B * c.T, heads * 64);
+  const int32_t* seg = segments_ptr(segments, qkv, causal);
   c10::DeviceGuard guard(qkv.device());
   gk::attn_fwd(qkv.data_ptr(), out.data_ptr(), lse.data_ptr<float>(), (int)c.B, (int)c.T, (int)heads, (float)p,
-               (uint32_t)seed, seed_word(seed_dev), c.key_bits, lo, causal, cur_stream(qkv));
+               (uint32_t)seed, seed_word(seed_dev), c.key_bits, lo, causal, seg, cur_stream(qkv));
 }
 
 void attn_bwd(at::Tensor qkv, at::Tensor out, at::Tensor dout, at::Tensor lse, at::Tensor delta, at::Tensor dqkv,
               int64_t heads, double p, int64_t seed, c10::optional<at::Tensor> seed_dev,
-              c10::optional<at::Tensor> key_bits, c10::optional<at::Tensor> out_lo, bool causal) {
+              c10::optional<at::Tensor> key_bits, c10::optional<at::Tensor> out_lo, bool causal,
+              c10::optional<at::Tensor> segments) {
   const AttnCall c = check_attn_call(at::kBFloat16, qkv, out, lse, heads, p, key_bits, &dout, &delta, &dqkv);
   const void* lo = out_lo_ptr(out_lo, c.key_bits, causal, c.B * c.T, heads * 64);
+  const int32_t* seg = segments_ptr(segments, qkv, causal);
   c10::DeviceGuard guard(qkv.device());
   gk::attn_bwd(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr<float>(), delta.data_ptr<float>(),
                dqkv.data_ptr(), (int)c.B, (int)c.T, (int)heads, (float)p, (uint32_t)seed, seed_word(seed_dev),
-               c.key_bits, lo, causal, cur_stream(qkv));
+               c.key_bits, lo, causal, seg, cur_stream(qkv));
 }
 
 void attn_f32_fwd(at::Tensor qkv, at::Tensor out, at::Tensor lse, int64_t heads, double p, int64_t seed,
-                  c10::optional<at::Tensor> seed_dev, c10::optional<at::Tensor> key_bits, bool causal) {
+                  c10::optional<at::Tensor> seed_dev, c10::optional<at::Tensor> key_bits, bool causal,
+                  c10::optional<at::Tensor> segments) {
   const AttnCall c = check_attn_call(at::kFloat, qkv, out, lse, heads, p, key_bits);
+  const int32_t* seg = segments_ptr(segments, qkv, causal);
   c10::DeviceGuard guard(qkv.device());
   gk::attn_f32_fwd(qkv.data_ptr<float>(), out.data_ptr<float>(), lse.data_ptr<float>(), (int)c.B, (int)c.T,
-                   (int)heads, (float)p, (uint32_t)seed, seed_word(seed_dev), c.key_bits, causal, cur_stream(qkv));
+                   (int)heads, (float)p, (uint32_t)seed, seed_word(seed_dev), c.key_bits, causal, seg,
+                   cur_stream(qkv));
 }
 
 void attn_f32_bwd(at::Tensor qkv, at::Tensor out, at::Tensor dout, at::Tensor lse, at::Tensor delta, at::Tensor dqkv,
                   int64_t heads, double p, int64_t seed, c10::optional<at::Tensor> seed_dev,
-                  c10::optional<at::Tensor> key_bits, bool causal) {
+                  c10::optional<at::Tensor> key_bits, bool causal, c10::optional<at::Tensor> segments) {
   const AttnCall c = check_attn_call(at::kFloat, qkv, out, lse, heads, p, key_bits, &dout, &delta, &dqkv);
+  const int32_t* seg = segments_ptr(segments, qkv, causal);
   c10::DeviceGuard guard(qkv.device());
   gk::attn_f32_bwd(qkv.data_ptr<float>(), out.data_ptr<float>(), dout.data_ptr<float>(), lse.data_ptr<float>(),
                    delta.data_ptr<float>(), dqkv.data_ptr<float>(), (int)c.B, (int)c.T, (int)heads, (float)p,
-                   (uint32_t)seed, seed_word(seed_dev), c.key_bits, causal, cur_stream(qkv));
+                   (uint32_t)seed, seed_word(seed_dev), c.key_bits, causal, seg, cur_stream(qkv));
 }
 
 // [B, T] key mask (nonzero = valid; any 1-, 2-, 4- or 8-byte dtype) -> packed bits int32 [B, T / 32]
@@ -2234,16 +2252,17 @@ TORCH_LIBRARY(gksgd, m) {
   m.def("attn_supported(int T, int D) -> bool",
         [](int64_t T, int64_t D) { return gk::attn_supported((int)T, (int)D); });
   m.def("attn_fwd(Tensor qkv, Tensor(a!) out, Tensor(b!) lse, int heads, float p, int seed, Tensor? seed_dev=None, "
-        "Tensor? key_bits=None, Tensor(c!)? out_lo=None, bool causal=False) -> ()");
+        "Tensor? key_bits=None, Tensor(c!)? out_lo=None, bool causal=False, Tensor? segments=None) -> ()");
   m.def("attn_pack_key_mask(Tensor mask, Tensor(a!) bits) -> ()");
   m.def("attn_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, Tensor(a!) delta, Tensor(b!) dqkv, int heads, "
         "float p, int seed, Tensor? seed_dev=None, Tensor? key_bits=None, Tensor? out_lo=None, "
-        "bool causal=False) -> ()");
+        "bool causal=False, Tensor? segments=None) -> ()");
   m.def("attn_dropout_mask(Tensor(a!) mask, int B, int heads, int T, float p, int seed, Tensor? seed_dev=None) -> ()");
   m.def("attn_f32_fwd(Tensor qkv, Tensor(a!) out, Tensor(b!) lse, int heads, float p, int seed, Tensor? seed_dev=None, "
-        "Tensor? key_bits=None, bool causal=False) -> ()");
+        "Tensor? key_bits=None, bool causal=False, Tensor? segments=None) -> ()");
   m.def("attn_f32_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, Tensor(a!) delta, Tensor(b!) dqkv, int heads, "
-        "float p, int seed, Tensor? seed_dev=None, Tensor? key_bits=None, bool causal=False) -> ()");
+        "float p, int seed, Tensor? seed_dev=None, Tensor? key_bits=None, bool causal=False, "
+        "Tensor? segments=None) -> ()");
   m.def("attn_f32_supported(int T, int D) -> bool",
         [](int64_t T, int64_t D) { return gk::attn_f32_supported((int)T, (int)D); });
   m.def("add_ln_supported(int H) -> bool", &add_ln_supported);

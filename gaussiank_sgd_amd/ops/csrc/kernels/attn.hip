@@ -36,14 +36,21 @@
 // (aswz) that is conflict-free both for the 16-row ds_read_b128 operand reads
 // and for the 8-row transposed reads, so Q / K tiles serve both.
 //
-// Dropout, the key-padding mask (MASK instantiations, with out_lo) and the
-// causal mask (CAUSAL instantiations): attn_common.h, shared with attn_f32.hip.
+// Dropout, the key-padding mask (MASK instantiations, with out_lo), the causal
+// mask (CAUSAL instantiations) and the document mask of packed sequences (DOC
+// instantiations of the causal ones): attn_common.h, shared with attn_f32.hip.
 #include "common.h"
 #include "gk_kernels.h"
 #include "mfma_util.h"
 #include "attn_common.h"
 
 namespace gk {
+
+// The DOC instantiations are a unit of their own, attn_docs.hip: this file's kernels again (GK_ATTN_DOC_UNIT),
+// built without the packed fp32 VALU ops, so that this unit's instantiations keep the code they have.
+void attn_doc_launch_fwd(const AttnArgsT<uint16_t>& a, dim3 grid, hipStream_t stream);
+void attn_doc_launch_bwd(const AttnArgsT<uint16_t>& a, dim3 grid, hipStream_t stream);
+
 namespace {
 
 constexpr int kTileB = kKT * kHD * 2;   // 8 KiB per [kKT rows][kHD] tile
@@ -160,8 +167,9 @@ using AttnArgs = AttnArgsT<uint16_t>;
 // tiles of 64 keys in a 3-deep LDS ring
 // ---------------------------------------------------------------------------
 // (MASK: held to the 3 workgroups per CU that the unmasked forward's register count already allows)
-template <bool DROP, bool MASK, bool CAUSAL = false>
+template <bool DROP, bool MASK, bool CAUSAL = false, bool DOC = false>
 __global__ void __launch_bounds__(64 * kAW, (MASK || CAUSAL) ? 3 : 2) attn_fwd_kernel(AttnArgs a) {
+  static_assert(CAUSAL || !DOC, "the document mask is a variant of the causal kernels");
   __shared__ __attribute__((aligned(1024))) char smem[kStages * 2 * kTileB];
   const uint32_t seed = DROP ? eff_seed(a) : 0u;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, g = lane >> 4;
@@ -179,6 +187,10 @@ __global__ void __launch_bounds__(64 * kAW, (MASK || CAUSAL) ? 3 : 2) attn_fwd_k
   const int64_t tstep = kKT * ld;
   const int nt = key_tiles<MASK, CAUSAL>(kbits, T, qb, lane);
   const int q0u = CAUSAL ? __builtin_amdgcn_readfirstlane(q0) : 0;   // wave-uniform: the tile cases (TileMask)
+  const int32_t* seg = DOC ? a.seg + (int64_t)b * 2 * T : nullptr;
+  const int t_lo = DOC ? DocRows::first_tile(seg, qb) : 0;           // first key tile, workgroup-uniform
+  DocRows doc;
+  if (DOC) doc.load(seg, q0u, li, g);
 
   bf16x8 qf[2][2];
 #pragma unroll
@@ -186,8 +198,8 @@ __global__ void __launch_bounds__(64 * kAW, (MASK || CAUSAL) ? 3 : 2) attn_fwd_k
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
       qf[qt][ks] = *reinterpret_cast<const bf16x8*>(base + h * kHD + (int64_t)(q0 + 16 * qt + li) * ld + 32 * ks + 8 * g);
-  dma.issue(0, 0, lds, wave);
-  if (nt > 1) dma.issue(tstep, tstep, lds + 2 * kTileB, wave);
+  dma.issue(t_lo * tstep, t_lo * tstep, lds, wave);
+  if (t_lo + 1 < nt) dma.issue((t_lo + 1) * tstep, (t_lo + 1) * tstep, lds + 2 * kTileB, wave);
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
@@ -210,14 +222,14 @@ __global__ void __launch_bounds__(64 * kAW, (MASK || CAUSAL) ? 3 : 2) attn_fwd_k
   int cur = 0, pre = 2;   // ring slots of tile t and of tile t + 2
   bool started = false, fresh[2] = {true, true};   // first_tile(), softmax_step()
   TileMask<MASK, CAUSAL> tm;
-  for (int t = 0; t < nt; ++t) {
+  for (int t = t_lo; t < nt; ++t) {
     tm.load(kbits, t);
     wait_tile<kPieces>(t + 1 >= nt);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     if (t + 2 < nt) dma.issue((t + 2) * tstep, (t + 2) * tstep, lds + pre * 2 * kTileB, wave);
     // skipped tile: the ring moves on (the wave has passed the tile's barrier and staged its pieces)
-    if (tm.skip(q0u, t)) {
+    if (tm.skip(q0u, t) || (DOC && doc.skip(t))) {
       cur = ring_next(cur);
       pre = ring_next(pre);
       continue;
@@ -227,6 +239,7 @@ __global__ void __launch_bounds__(64 * kAW, (MASK || CAUSAL) ? 3 : 2) attn_fwd_k
     // S^T - m (log2 units), the running max as the initial accumulator
     f32x4 s[2][4];
     if (MASK || CAUSAL) tm.init(s, {-m[0], -m[1]}, li, g);
+    if (DOC) doc.mask(s);
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt) {
       const bf16x8 k0 = *reinterpret_cast<const bf16x8*>(Ks + aoff(16 * kt + li, g));
@@ -238,7 +251,8 @@ __global__ void __launch_bounds__(64 * kAW, (MASK || CAUSAL) ? 3 : 2) attn_fwd_k
     const bool first = first_tile<MASK>(started, t);
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt)
-      softmax_step<DROP, MASK, CAUSAL>(s[qt], o[qt], m[qt], l[qt], fresh[qt], first, hrow[qt], t, seed, a.thr);
+      // DOC: a row's first tiles may be all -inf, as under CAUSAL && MASK: the per-row first-tile step
+      softmax_step<DROP, MASK || DOC, CAUSAL>(s[qt], o[qt], m[qt], l[qt], fresh[qt], first, hrow[qt], t, seed, a.thr);
 
     const uint32_t vb = lbase + cur * 2 * kTileB + kTileB;
     cur = ring_next(cur);
@@ -266,7 +280,7 @@ __global__ void __launch_bounds__(64 * kAW, (MASK || CAUSAL) ? 3 : 2) attn_fwd_k
       for (int qt = 0; qt < 2; ++qt) o[qt][dt] = mfma(vf[dt], pf[qt][1], o[qt][dt]);
   }
 
-  if (MASK && nt == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // tile 0's LDS-DMA
+  if (MASK && (DOC ? nt <= t_lo : nt == 0)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the first tile's LDS-DMA
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
     const int q = q0 + 16 * qt + li;
@@ -287,8 +301,9 @@ __global__ void __launch_bounds__(64 * kAW, (MASK || CAUSAL) ? 3 : 2) attn_fwd_k
 // tile S^T = c K Q^T - lse, dZ^T = V dO^T - delta', dS^T = P^T (dP^T - delta),
 // dQ^T += K^T dS^T
 // ---------------------------------------------------------------------------
-template <bool DROP, bool MASK, bool CAUSAL = false>
+template <bool DROP, bool MASK, bool CAUSAL = false, bool DOC = false>
 __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_dq_kernel(AttnArgs a) {
+  static_assert(CAUSAL || !DOC, "the document mask is a variant of the causal kernels");
   __shared__ __attribute__((aligned(1024))) char smem[kStages * 2 * kTileB];
   const uint32_t seed = DROP ? eff_seed(a) : 0u;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, g = lane >> 4;
@@ -306,6 +321,10 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_dq_kernel(AttnArgs a) {
   const int64_t tstep = kKT * ld;
   const int nt = key_tiles<MASK, CAUSAL>(kbits, T, qb, lane);   // the forward's tile count and tile cases
   const int q0u = CAUSAL ? __builtin_amdgcn_readfirstlane(q0) : 0;
+  const int32_t* seg = DOC ? a.seg + (int64_t)b * 2 * T : nullptr;
+  const int t_lo = DOC ? DocRows::first_tile(seg, qb) : 0;
+  DocRows doc;
+  if (DOC) doc.load(seg, q0u, li, g);
 
   bf16x8 qf[2][2], df[2][2], of[2][2];
   // MASK: the rounding residue of the output (zero without out_lo).  With few valid keys P is concentrated,
@@ -330,8 +349,8 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_dq_kernel(AttnArgs a) {
     }
     nlse[qt] = -a.lse[(int64_t)bh * T + q];
   }
-  dma.issue(0, 0, lds, wave);
-  if (nt > 1) dma.issue(tstep, tstep, lds + 2 * kTileB, wave);
+  dma.issue(t_lo * tstep, t_lo * tstep, lds, wave);
+  if (t_lo + 1 < nt) dma.issue((t_lo + 1) * tstep, (t_lo + 1) * tstep, lds + 2 * kTileB, wave);
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
     const int q = q0 + 16 * qt + li;
@@ -364,14 +383,14 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_dq_kernel(AttnArgs a) {
 
   int cur = 0, pre = 2;   // ring slots of tile t and of tile t + 2
   TileMask<MASK, CAUSAL> tm;
-  for (int t = 0; t < nt; ++t) {
+  for (int t = t_lo; t < nt; ++t) {
     tm.load(kbits, t);
-    // the delta stores follow tile 1's pieces: drain everything on the first tile
-    wait_tile<kPieces>(t == 0 || t + 1 >= nt);
+    // the delta stores follow the second tile's pieces: drain everything on the first tile
+    wait_tile<kPieces>(t == t_lo || t + 1 >= nt);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     if (t + 2 < nt) dma.issue((t + 2) * tstep, (t + 2) * tstep, lds + pre * 2 * kTileB, wave);
-    if (tm.skip(q0u, t)) {
+    if (tm.skip(q0u, t) || (DOC && doc.skip(t))) {
       cur = ring_next(cur);
       pre = ring_next(pre);
       continue;
@@ -381,6 +400,7 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_dq_kernel(AttnArgs a) {
 
     f32x4 s[2][4], dz[2][4];
     if (MASK || CAUSAL) tm.init(s, nlse, li, g);
+    if (DOC) doc.mask(s);
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt) {
       const bf16x8 k0 = *reinterpret_cast<const bf16x8*>(Ks + aoff(16 * kt + li, g));
@@ -422,7 +442,7 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_dq_kernel(AttnArgs a) {
       for (int qt = 0; qt < 2; ++qt) dq[qt][dt] = mfma(kf[dt], pf[qt][1], dq[qt][dt]);
   }
 
-  if (MASK && nt == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // tile 0's LDS-DMA
+  if (MASK && (DOC ? nt <= t_lo : nt == 0)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the first tile's LDS-DMA
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
     const int q = q0 + 16 * qt + li;
@@ -441,8 +461,9 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_dq_kernel(AttnArgs a) {
 // ---------------------------------------------------------------------------
 constexpr int kKvBuf = 2 * kTileB + 512;   // Q tile, dO tile, lse[64], delta[64]
 
-template <bool DROP, bool MASK, bool CAUSAL = false>
+template <bool DROP, bool MASK, bool CAUSAL = false, bool DOC = false>
 __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_kv_kernel(AttnArgs a) {
+  static_assert(CAUSAL || !DOC, "the document mask is a variant of the causal kernels");
   __shared__ __attribute__((aligned(1024))) char smem[kStages * kKvBuf];
   const uint32_t seed = DROP ? eff_seed(a) : 0u;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, g = lane >> 4;
@@ -484,10 +505,14 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_kv_kernel(AttnArgs a) {
     if (wave < 2)
       __builtin_amdgcn_global_load_lds((wave ? delp : lsep) + t * kKT + lane, dst + 2 * kTileB + wave * 256, 4, 0, 0);
   };
-  const int nt = T / kKT;
-  // CAUSAL: the first query tile that sees any of the workgroup's keys (nt is even, so t0 + 1 < nt)
+  // CAUSAL: the first query tile that sees any of the workgroup's keys (T / kKT is even, so t0 + 1 < T / kKT)
   const int t0 = CAUSAL ? 2 * kb : 0;
   const int k0u = CAUSAL ? __builtin_amdgcn_readfirstlane(k0) : 0;   // wave-uniform: the tile cases below
+  // DOC: the loop ends with the document of the workgroup's last key (it may then be a single tile)
+  const int32_t* seg_end = DOC ? a.seg + ((int64_t)b * 2 + 1) * T : nullptr;
+  const int nt = DOC ? DocKeys::end_tile(seg_end, kb, t0, T / kKT) : T / kKT;
+  DocKeys doc;
+  if (DOC) doc.load(seg_end, k0u, li);
 
   bf16x8 kf[2][2], vf[2][2];
 #pragma unroll
@@ -538,6 +563,8 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_kv_kernel(AttnArgs a) {
     // masked element-wise; later tiles see all 32 keys
     const int krel = CAUSAL ? kKT * t - k0u : 0;
     if (CAUSAL && krel < -63) continue;
+    if (DOC && doc.past(t)) continue;   // every query of the tile is in a later document than the wave's keys
+    const bool doc_edge = DOC && !doc.inside(t);
 
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
@@ -573,6 +600,12 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_kv_kernel(AttnArgs a) {
         for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
           for (int kt = 0; kt < 2; ++kt) causal_scores_q(s[qt][kt], krel + 32 * half + 16 * qt + 4 * g - 16 * kt - li);
+      }
+      if (doc_edge) {   // queries of a later document than the key's: P = 0
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+          for (int kt = 0; kt < 2; ++kt) doc_scores_q(s[qt][kt], doc.e[kt] - (kKT * t + 32 * half + 16 * qt + 4 * g));
       }
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt) {
@@ -652,6 +685,25 @@ __global__ void __launch_bounds__(64 * kAW, 2) attn_bwd_kv_kernel(AttnArgs a) {
   }
 }
 
+#ifdef GK_ATTN_DOC_UNIT
+// attn_docs.hip: this file up to here, for the DOC instantiations alone
+}  // namespace
+
+void attn_doc_launch_fwd(const AttnArgs& a, dim3 grid, hipStream_t stream) {
+  attn_dispatch(a.thr != 0, a.key_bits != nullptr, true, [&](auto d, auto m, auto) {
+    hipLaunchKernelGGL((attn_fwd_kernel<d(), m(), true, true>), grid, dim3(64 * kAW), 0, stream, a);
+  });
+}
+
+void attn_doc_launch_bwd(const AttnArgs& a, dim3 grid, hipStream_t stream) {
+  attn_dispatch(a.thr != 0, a.key_bits != nullptr, true, [&](auto d, auto m, auto) {
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<d(), m(), true, true>), grid, dim3(64 * kAW), 0, stream, a);
+    hipLaunchKernelGGL((attn_bwd_kv_kernel<d(), m(), true, true>), grid, dim3(64 * kAW), 0, stream, a);
+  });
+}
+
+}  // namespace gk
+#else
 // keep mask [B*H][T][T] as bytes, from the same pair hashes
 __global__ void attn_dropout_mask_kernel(uint8_t* __restrict__ mask, int64_t npairs, AttnArgs a, uint32_t thr) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -679,12 +731,14 @@ __global__ void __launch_bounds__(256) attn_pack_key_mask_kernel(const E* __rest
 }
 
 void launch_fwd(const AttnArgs& a, bool causal, dim3 grid, hipStream_t stream) {
+  if (a.seg != nullptr) return attn_doc_launch_fwd(a, grid, stream);
   attn_dispatch(a.thr != 0, a.key_bits != nullptr, causal, [&](auto d, auto m, auto c) {
     hipLaunchKernelGGL((attn_fwd_kernel<d(), m(), c()>), grid, dim3(64 * kAW), 0, stream, a);
   });
 }
 
 void launch_bwd(const AttnArgs& a, bool causal, dim3 grid, hipStream_t stream) {
+  if (a.seg != nullptr) return attn_doc_launch_bwd(a, grid, stream);
   attn_dispatch(a.thr != 0, a.key_bits != nullptr, causal, [&](auto d, auto m, auto c) {
     hipLaunchKernelGGL((attn_bwd_dq_kernel<d(), m(), c()>), grid, dim3(64 * kAW), 0, stream, a);
     hipLaunchKernelGGL((attn_bwd_kv_kernel<d(), m(), c()>), grid, dim3(64 * kAW), 0, stream, a);
@@ -696,8 +750,10 @@ void launch_bwd(const AttnArgs& a, bool causal, dim3 grid, hipStream_t stream) {
 bool attn_supported(int T, int D) { return D == kHD && T >= kRows && T % kRows == 0; }
 
 void attn_fwd(const void* qkv, void* out, float* lse, int B, int T, int H, float p, uint32_t seed,
-              const uint32_t* seed_dev, const uint32_t* key_bits, void* out_lo, bool causal, hipStream_t stream) {
+              const uint32_t* seed_dev, const uint32_t* key_bits, void* out_lo, bool causal, const int32_t* seg,
+              hipStream_t stream) {
   AttnArgs a = make_args<uint16_t>(T, H, p, seed, seed_dev);
+  a.seg = causal ? seg : nullptr;
   a.out_lo = (key_bits || causal) ? static_cast<uint16_t*>(out_lo) : nullptr;
   a.qkv = static_cast<const uint16_t*>(qkv);
   a.o = static_cast<uint16_t*>(out);
@@ -709,8 +765,9 @@ void attn_fwd(const void* qkv, void* out, float* lse, int B, int T, int H, float
 
 void attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int B,
               int T, int H, float p, uint32_t seed, const uint32_t* seed_dev, const uint32_t* key_bits,
-              const void* out_lo, bool causal, hipStream_t stream) {
+              const void* out_lo, bool causal, const int32_t* seg, hipStream_t stream) {
   AttnArgs a = make_args<uint16_t>(T, H, p, seed, seed_dev);
+  a.seg = causal ? seg : nullptr;
   a.key_bits = key_bits;
   a.out_lo = (key_bits || causal) ? static_cast<uint16_t*>(const_cast<void*>(out_lo)) : nullptr;
   a.qkv = static_cast<const uint16_t*>(qkv);
@@ -752,3 +809,4 @@ void attn_dropout_mask(uint8_t* mask, int B, int H, int T, float p, uint32_t see
 }
 
 }  // namespace gk
+#endif  // GK_ATTN_DOC_UNIT

@@ -38,6 +38,25 @@
 // kept as under MASK: the first rows of a sequence see few keys.
 // The CAUSAL = false instantiations are the code without any of this.
 //
+// Document mask (DOC instantiations, CAUSAL only): a sequence is a run of documents laid end to end, and
+// query q sees key k iff start[q] <= k <= q, i.e. k <= q <= end[k], ANDed with the key bits under MASK.
+// seg: int32 [B, 2, T], row 0 = start (index of the first token of the token's document), row 1 = end (of
+// its last token); both nondecreasing with start[t] <= t <= end[t].  The forward and the dQ kernel start
+// their key tiles at t_lo = start[128 qb] / 64 (the block's first row has the earliest document) and stop
+// where causal / MASK stop them; the ring prologue and the tile offsets start from t_lo, the dropout hash
+// index stays a function of the absolute key.  Per wave a tile lies wholly before start[q0] (arithmetic
+// skipped, barrier and staging kept), at or after start[q0 + 31] (no document work), or is masked
+// element-wise through the accumulator init (key - start[q] < 0, the sign trick of causal_scores_t).  A row
+// of a wave may then meet tiles that are all -inf before its first visible one, so DOC takes the per-row
+// `fresh` first-tile step and the per-row lazy max of CAUSAL && MASK; out_lo is kept as under CAUSAL.  The
+// dK/dV kernel runs its query tiles from 2 kb to end[128 kb + 127] / 64 + 1; per wave a tile lies wholly
+// after end[k0 + 31] (skipped), wholly at or before end[k0] (no document work) or is masked element-wise
+// (end[key] - query < 0).  Every tile bound read from seg is clamped into the range causal alone would
+// visit, so a malformed tensor gives wrong numbers but never an out-of-range tile address.  The block
+// order stays the causal heaviest-first one (causal_block), which documents make approximate: a row block
+// deep inside a late document costs fewer tiles than its position says.
+// The DOC = false instantiations are the code without any of this.
+//
 // Lazy running max (forward): only when some row's tile max exceeds the
 // current m by kLazy (log2 units, so p <= 256) does the wave take the textbook
 // update (cross-lane row max, O and l rescale).  The first tile always takes
@@ -77,6 +96,7 @@ struct AttnArgsT {
   uint32_t thr;       // drop threshold on 16 hash bits
   uint32_t seed;
   const uint32_t* key_bits;   // optional [B, T / 32] valid-key bits, MASK kernels only
+  const int32_t* seg;         // optional [B, 2, T] document start / end per token, DOC kernels only (null = none)
   // optional, bf16 MASK / CAUSAL kernels only (null for fp32): what the bf16 rounding of the output dropped,
   // out_lo = bf16(O - out) [B, T, H, 64], written by the forward and added back by the dQ kernel for delta
   E* out_lo;
@@ -108,7 +128,8 @@ AttnArgsT<E> make_args(int T, int H, float p, uint32_t seed, const uint32_t* see
   return a;
 }
 
-// (thr != 0, key_bits != nullptr, causal) -> f(DROP, MASK, CAUSAL) with std::bool_constant arguments
+// (thr != 0, key_bits != nullptr, causal) -> f(DROP, MASK, CAUSAL) with std::bool_constant arguments.  The DOC
+// instantiations (seg != nullptr, always causal) are dispatched the same way in their own units
 template <typename F>
 void attn_dispatch(bool drop, bool mask, bool causal, F&& f) {
   auto with_causal = [&](auto d, auto m) {
@@ -240,6 +261,77 @@ __device__ __forceinline__ void causal_scores_q(f32x4& s, int d) {
     s[r] = fminf(s[r], __uint_as_float(0x7f800000u | neg));
   }
 }
+
+// document mask on a boundary tile, forward / dQ layout: d[qt] = (tile's first key) + 4g - start[lane's
+// query of block qt], so key (kt, r) is hidden from that query iff d[qt] + 16 kt + r < 0
+__device__ __forceinline__ void doc_scores_t(f32x4 (&s)[2][4], int d0, int d1) {
+#pragma unroll
+  for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const uint32_t neg = (uint32_t)((qt ? d1 : d0) + (16 * kt + r)) & 0x80000000u;   // sign set = hidden
+        s[qt][kt][r] = fminf(s[qt][kt][r], __uint_as_float(0x7f800000u | neg));
+      }
+}
+
+// the same in the dK/dV kernels' layout: d = end[lane's key] - (query of r = 0); score r is hidden iff d - r < 0
+__device__ __forceinline__ void doc_scores_q(f32x4& s, int d) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const uint32_t neg = (uint32_t)(d - r) & 0x80000000u;
+    s[r] = fminf(s[r], __uint_as_float(0x7f800000u | neg));
+  }
+}
+
+// DOC, forward and dQ kernels: the rows' document starts beside TileMask.  load() once per workgroup, then per
+// tile skip() where TileMask::skip() is asked and mask() after TileMask::init().
+struct DocRows {
+  int s_lo, s_hi;   // start[] of the wave's first and last query (wave-uniform; start is nondecreasing)
+  int d[2];         // 4g - start[q0 + 16 qt + li]
+  int key0;         // the current tile's first key
+
+  // first key tile of row block qb: that of its first row's document, clamped to the causal range [0, 2 qb]
+  static __device__ __forceinline__ int first_tile(const int32_t* start, int qb) {
+    return min(max(__builtin_amdgcn_readfirstlane(start[kRows * qb]) / kKT, 0), 2 * qb);
+  }
+  __device__ __forceinline__ void load(const int32_t* start, int q0u, int li, int g) {
+    s_lo = __builtin_amdgcn_readfirstlane(start[q0u]);
+    s_hi = __builtin_amdgcn_readfirstlane(start[q0u + 31]);
+    d[0] = 4 * g - start[q0u + li];
+    d[1] = 4 * g - start[q0u + 16 + li];
+  }
+  // every key of the tile lies before the wave's earliest document
+  __device__ __forceinline__ bool skip(int t) {
+    key0 = kKT * t;
+    return key0 + kKT - 1 < s_lo;
+  }
+  __device__ __forceinline__ void mask(f32x4 (&s)[2][4]) const {
+    if (key0 < s_hi) doc_scores_t(s, d[0] + key0, d[1] + key0);
+  }
+};
+
+// DOC, dK/dV kernels: the keys' document ends.  Query tile t of the wave is past() (skipped), or masked
+// element-wise unless inside()
+struct DocKeys {
+  int e_lo, e_hi;   // end[] of the wave's first and last key (wave-uniform; end is nondecreasing)
+  int e[2];         // end[k0 + 16 kt + li]
+
+  // one past the last query tile of key block kb: that of its last key's document, at least the causal
+  // loop's first tile (t0 = 2 kb) and at most nt
+  static __device__ __forceinline__ int end_tile(const int32_t* end, int kb, int t0, int nt) {
+    return min(max(__builtin_amdgcn_readfirstlane(end[kRows * kb + kRows - 1]) / kKT + 1, t0 + 1), nt);
+  }
+  __device__ __forceinline__ void load(const int32_t* end, int k0u, int li) {
+    e_lo = __builtin_amdgcn_readfirstlane(end[k0u]);
+    e_hi = __builtin_amdgcn_readfirstlane(end[k0u + 31]);
+    e[0] = end[k0u + li];
+    e[1] = end[k0u + 16 + li];
+  }
+  __device__ __forceinline__ bool past(int t) const { return kKT * t > e_hi; }
+  __device__ __forceinline__ bool inside(int t) const { return kKT * t + kKT - 1 <= e_lo; }
+};
 
 // Per-tile mask front end of the forward and dQ kernels, in the order a kernel needs it: load() before
 // the tile's wait and barrier, skip() after the next tile is staged, init() ahead of the operand reads.

@@ -35,13 +35,21 @@
 // Dropout, the key-padding mask (MASK instantiations; no out_lo: the fp32
 // output has no rounding residue worth keeping) and the causal mask (CAUSAL
 // instantiations; the dK/dV kernel starts at an even query tile, so the two
-// stages keep their parity): attn_common.h, shared with attn.hip.
+// stages keep their parity) and the document mask (DOC instantiations of the
+// causal ones; the forward and dQ loops start at tile t_lo in stage t_lo & 1):
+// attn_common.h, shared with attn.hip.
 #include "common.h"
 #include "gk_kernels.h"
 #include "mfma_util.h"
 #include "attn_common.h"
 
 namespace gk {
+
+// The DOC instantiations are a unit of their own, attn_f32_docs.hip: this file's kernels again
+// (GK_ATTN_DOC_UNIT), built without the packed fp32 VALU ops, so that this unit's instantiations keep their code.
+void attn_f32_doc_launch_fwd(int nb, const AttnArgsT<float>& a, hipStream_t stream);
+void attn_f32_doc_launch_bwd(int nb, const AttnArgsT<float>& a, hipStream_t stream);
+
 namespace {
 
 constexpr int kFTile = kKT * kHD * 4;       // 16 KiB per [kKT rows][kHD] tile
@@ -92,8 +100,9 @@ __device__ __forceinline__ float ld1(const char* lds, uint32_t off) { return *re
 // ---------------------------------------------------------------------------
 // forward: 4 waves x 32 queries of one (batch, head); K / V tiles of 64 keys
 // ---------------------------------------------------------------------------
-template <bool DROP, bool MASK, bool CAUSAL = false>
+template <bool DROP, bool MASK, bool CAUSAL = false, bool DOC = false>
 __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Args a) {
+  static_assert(CAUSAL || !DOC, "the document mask is a variant of the causal kernels");
   extern __shared__ __attribute__((aligned(1024))) char smem[];   // 2 stages x (K, V)
   const uint32_t seed = DROP ? eff_seed(a) : 0u;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -111,9 +120,13 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Arg
   dv.init(base + (int64_t)(2 * H + h) * kHD, ld, wave, lane);
   const int64_t tstep = kKT * ld;
   const uint32_t* kbits = MASK ? a.key_bits + (int64_t)b * (T >> 5) : nullptr;
+  const int32_t* seg = DOC ? a.seg + (int64_t)b * 2 * T : nullptr;
+  const int t_lo = DOC ? DocRows::first_tile(seg, qb) : 0;   // first key tile, workgroup-uniform
+  DocRows doc;
+  if (DOC) doc.load(seg, q0, li, g);
 
-  dk.issue(0, lds, wave);
-  dv.issue(0, lds + kFTile, wave);
+  dk.issue(t_lo * tstep, lds + (t_lo & 1) * 2 * kFTile, wave);
+  dv.issue(t_lo * tstep, lds + (t_lo & 1) * 2 * kFTile + kFTile, wave);
   const int nt = key_tiles<MASK, CAUSAL>(kbits, T, qb, lane);
   f32x4 qf[2][4];
 #pragma unroll
@@ -135,7 +148,7 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Arg
 
   bool started = false, fresh[2] = {true, true};   // first_tile(), softmax_step()
   TileMask<MASK, CAUSAL> tm;
-  for (int t = 0; t < nt; ++t) {
+  for (int t = t_lo; t < nt; ++t) {
     tm.load(kbits, t);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of tile t
     __builtin_amdgcn_s_barrier();                        // everyone's pieces; tile t - 1 consumed
@@ -147,11 +160,12 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Arg
       dk.issue((t + 1) * tstep, nx, wave);
       dv.issue((t + 1) * tstep, nx + kFTile, wave);
     }
-    if (tm.skip(q0, t)) continue;   // q0 is wave-uniform (wave is)
+    if (tm.skip(q0, t) || (DOC && doc.skip(t))) continue;   // q0 is wave-uniform (wave is)
 
     // S^T - m (log2 units)
     f32x4 s[2][4];
     tm.init(s, {-m[0], -m[1]}, li, g);
+    if (DOC) doc.mask(s);
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
@@ -163,7 +177,8 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Arg
     const bool first = first_tile<MASK>(started, t);
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt)
-      softmax_step<DROP, MASK, CAUSAL>(s[qt], o[qt], m[qt], l[qt], fresh[qt], first, hrow[qt], t, seed, a.thr);
+      // DOC: a row's first tiles may be all -inf, as under CAUSAL && MASK: the per-row first-tile step
+      softmax_step<DROP, MASK || DOC, CAUSAL>(s[qt], o[qt], m[qt], l[qt], fresh[qt], first, hrow[qt], t, seed, a.thr);
 
     // O^T += V^T P^T: MFMA j contracts keys 16 kt + 4g + j
 #pragma unroll
@@ -180,7 +195,7 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Arg
       }
   }
 
-  if (MASK && nt == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // tile 0's LDS-DMA
+  if (MASK && (DOC ? nt <= t_lo : nt == 0)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the first tile's LDS-DMA
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
     const int q = q0 + 16 * qt + li;
@@ -195,8 +210,9 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_fwd_kernel(AttnF32Arg
 // backward, dQ (+ delta = rowsum(dO * O)): per key tile S^T = c K Q^T - lse,
 // dZ^T = V dO^T - delta', dS^T = P^T (dP^T - delta), dQ^T += K^T dS^T
 // ---------------------------------------------------------------------------
-template <bool DROP, bool MASK, bool CAUSAL = false>
+template <bool DROP, bool MASK, bool CAUSAL = false, bool DOC = false>
 __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_dq_kernel(AttnF32Args a) {
+  static_assert(CAUSAL || !DOC, "the document mask is a variant of the causal kernels");
   extern __shared__ __attribute__((aligned(1024))) char smem[];   // 2 stages x (K, V)
   const uint32_t seed = DROP ? eff_seed(a) : 0u;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -214,9 +230,13 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_dq_kernel(AttnF32
   dv.init(base + (int64_t)(2 * H + h) * kHD, ld, wave, lane);
   const int64_t tstep = kKT * ld;
   const uint32_t* kbits = MASK ? a.key_bits + (int64_t)b * (T >> 5) : nullptr;
+  const int32_t* seg = DOC ? a.seg + (int64_t)b * 2 * T : nullptr;
+  const int t_lo = DOC ? DocRows::first_tile(seg, qb) : 0;   // first key tile, workgroup-uniform
+  DocRows doc;
+  if (DOC) doc.load(seg, q0, li, g);
 
-  dk.issue(0, lds, wave);
-  dv.issue(0, lds + kFTile, wave);
+  dk.issue(t_lo * tstep, lds + (t_lo & 1) * 2 * kFTile, wave);
+  dv.issue(t_lo * tstep, lds + (t_lo & 1) * 2 * kFTile + kFTile, wave);
   const int nt = key_tiles<MASK, CAUSAL>(kbits, T, qb, lane);
   f32x4 qf[2][4], df[2][4];
   float nlse[2], del[2], ndel[2];
@@ -250,7 +270,7 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_dq_kernel(AttnF32
     for (int dt = 0; dt < 4; ++dt) dq[qt][dt] = splat4(0.f);
 
   TileMask<MASK, CAUSAL> tm;
-  for (int t = 0; t < nt; ++t) {
+  for (int t = t_lo; t < nt; ++t) {
     tm.load(kbits, t);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -262,7 +282,7 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_dq_kernel(AttnF32
       dk.issue((t + 1) * tstep, nx, wave);
       dv.issue((t + 1) * tstep, nx + kFTile, wave);
     }
-    if (tm.skip(q0, t)) continue;
+    if (tm.skip(q0, t) || (DOC && doc.skip(t))) continue;
 
     f32x4 s[2][4], dz[2][4];
 #pragma unroll
@@ -270,6 +290,7 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_dq_kernel(AttnF32
 #pragma unroll
       for (int kt = 0; kt < 4; ++kt) dz[qt][kt] = splat4(ndel[qt]);
     tm.init(s, nlse, li, g);
+    if (DOC) doc.mask(s);
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt) {
 #pragma unroll
@@ -303,7 +324,7 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_dq_kernel(AttnF32
       }
   }
 
-  if (MASK && nt == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // tile 0's LDS-DMA
+  if (MASK && (DOC ? nt <= t_lo : nt == 0)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the first tile's LDS-DMA
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
     const int q = q0 + 16 * qt + li;
@@ -321,8 +342,9 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_dq_kernel(AttnF32
 // ---------------------------------------------------------------------------
 constexpr int kKvStage = 2 * kFTile + 512;   // Q tile, dO tile, lse[64], delta[64]
 
-template <bool DROP, bool MASK, bool CAUSAL = false>
+template <bool DROP, bool MASK, bool CAUSAL = false, bool DOC = false>
 __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_kv_kernel(AttnF32Args a) {
+  static_assert(CAUSAL || !DOC, "the document mask is a variant of the causal kernels");
   extern __shared__ __attribute__((aligned(1024))) char smem[];   // 2 x kKvStage
   const uint32_t seed = DROP ? eff_seed(a) : 0u;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -366,9 +388,13 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_kv_kernel(AttnF32
     if (wave < 2)
       __builtin_amdgcn_global_load_lds((wave ? delp : lsep) + t * kKT + lane, dst + 2 * kFTile + wave * 256, 4, 0, 0);
   };
-  const int nt = T / kKT;
   // CAUSAL: the first query tile that sees any of the workgroup's keys (even, so the stages keep t & 1)
   const int t0 = CAUSAL ? 2 * kb : 0;
+  // DOC: the loop ends with the document of the workgroup's last key
+  const int32_t* seg_end = DOC ? a.seg + ((int64_t)b * 2 + 1) * T : nullptr;
+  const int nt = DOC ? DocKeys::end_tile(seg_end, kb, t0, T / kKT) : T / kKT;
+  DocKeys doc;
+  if (DOC) doc.load(seg_end, k0, li);
 
   stage(t0, 0);
   f32x4 kf[2][4], vf[2][4];
@@ -403,6 +429,8 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_kv_kernel(AttnF32
     // masked element-wise; later tiles see all 32 keys
     const int krel = CAUSAL ? kKT * t - k0 : 0;
     if (CAUSAL && krel < -63) continue;
+    if (DOC && doc.past(t)) continue;   // every query of the tile is in a later document than the wave's keys
+    const bool doc_edge = DOC && !doc.inside(t);
 
 #pragma unroll 1
     for (int qt = 0; qt < 4; ++qt) {   // not unrolled: one 16-query tile's operands live at a time
@@ -435,6 +463,10 @@ __global__ void __launch_bounds__(64 * kWaves, 2) attn_f32_bwd_kv_kernel(AttnF32
       if (CAUSAL && krel < 31) {   // hidden (query, key) pairs: P = 0
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt) causal_scores_q(s[kt], krel + qr - 16 * kt - li);
+      }
+      if (doc_edge) {   // queries of a later document than the key's: P = 0
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt) doc_scores_q(s[kt], doc.e[kt] - (kKT * t + qr));
       }
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt) {
@@ -492,13 +524,34 @@ void launch(K kern, int nblocks, int lds, const AttnF32Args& a, hipStream_t stre
   hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(64 * kWaves), lds, stream, a);
 }
 
+#ifdef GK_ATTN_DOC_UNIT
+// attn_f32_docs.hip: this file up to here, for the DOC instantiations alone
+}  // namespace
+
+void attn_f32_doc_launch_fwd(int nb, const AttnF32Args& a, hipStream_t stream) {
+  attn_dispatch(a.thr != 0, a.key_bits != nullptr, true, [&](auto d, auto m, auto) {
+    launch(attn_f32_fwd_kernel<d(), m(), true, true>, nb, 4 * kFTile, a, stream);
+  });
+}
+
+void attn_f32_doc_launch_bwd(int nb, const AttnF32Args& a, hipStream_t stream) {
+  attn_dispatch(a.thr != 0, a.key_bits != nullptr, true, [&](auto d, auto m, auto) {
+    launch(attn_f32_bwd_dq_kernel<d(), m(), true, true>, nb, 4 * kFTile, a, stream);
+    launch(attn_f32_bwd_kv_kernel<d(), m(), true, true>, nb, 2 * kKvStage, a, stream);
+  });
+}
+
+}  // namespace gk
+#else
 void launch_fwd(int nb, const AttnF32Args& a, bool causal, hipStream_t stream) {
+  if (a.seg != nullptr) return attn_f32_doc_launch_fwd(nb, a, stream);
   attn_dispatch(a.thr != 0, a.key_bits != nullptr, causal, [&](auto d, auto m, auto c) {
     launch(attn_f32_fwd_kernel<d(), m(), c()>, nb, 4 * kFTile, a, stream);
   });
 }
 
 void launch_bwd(int nb, const AttnF32Args& a, bool causal, hipStream_t stream) {
+  if (a.seg != nullptr) return attn_f32_doc_launch_bwd(nb, a, stream);
   attn_dispatch(a.thr != 0, a.key_bits != nullptr, causal, [&](auto d, auto m, auto c) {
     launch(attn_f32_bwd_dq_kernel<d(), m(), c()>, nb, 4 * kFTile, a, stream);
     launch(attn_f32_bwd_kv_kernel<d(), m(), c()>, nb, 2 * kKvStage, a, stream);
@@ -510,8 +563,10 @@ void launch_bwd(int nb, const AttnF32Args& a, bool causal, hipStream_t stream) {
 bool attn_f32_supported(int T, int D) { return D == kHD && T >= kRows && T % kRows == 0; }
 
 void attn_f32_fwd(const float* qkv, float* out, float* lse, int B, int T, int H, float p, uint32_t seed,
-                  const uint32_t* seed_dev, const uint32_t* key_bits, bool causal, hipStream_t stream) {
+                  const uint32_t* seed_dev, const uint32_t* key_bits, bool causal, const int32_t* seg,
+                  hipStream_t stream) {
   AttnF32Args a = make_args<float>(T, H, p, seed, seed_dev);
+  a.seg = causal ? seg : nullptr;
   a.qkv = qkv;
   a.o = out;
   a.lse = lse;
@@ -522,8 +577,9 @@ void attn_f32_fwd(const float* qkv, float* out, float* lse, int B, int T, int H,
 
 void attn_f32_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* delta, float* dqkv,
                   int B, int T, int H, float p, uint32_t seed, const uint32_t* seed_dev, const uint32_t* key_bits,
-                  bool causal, hipStream_t stream) {
+                  bool causal, const int32_t* seg, hipStream_t stream) {
   AttnF32Args a = make_args<float>(T, H, p, seed, seed_dev);
+  a.seg = causal ? seg : nullptr;
   a.qkv = qkv;
   a.out = out;
   a.dout = dout;
@@ -536,3 +592,4 @@ void attn_f32_bwd(const float* qkv, const float* out, const float* dout, const f
 }
 
 }  // namespace gk
+#endif  // GK_ATTN_DOC_UNIT
