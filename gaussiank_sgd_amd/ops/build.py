@@ -69,6 +69,7 @@ HIP_SOURCES = [
     "kernels/attn_f32_docs.hip",
     "kernels/embed.hip",
     "kernels/xent.hip",
+    "kernels/fp8.hip",
     "kernels/winograd.hip",
     "kernels/wino_x6.hip",
     "kernels/stem_f32.hip",
@@ -91,6 +92,7 @@ EXTRA_FLAGS = {"kernels/scatter.hip": ["-ffp-contract=off"],
                "kernels/ln_pre.hip": NO_PK_F32,
                "kernels/attn_docs.hip": NO_PK_F32,
                "kernels/attn_f32_docs.hip": NO_PK_F32,
+               "kernels/fp8.hip": NO_PK_F32,
                **{"kernels/gemm_inst_%s.hip" % f: ["-fno-slp-vectorize"] for f in set(GEMM_UNIT_FAMILY)}}
 
 

@@ -1731,6 +1731,91 @@ void xent_backward(at::Tensor logits, at::Tensor labels, at::Tensor lse, at::Ten
                     grad.data_ptr(), R, (int)V, ignore, cur_stream(logits));
 }
 
+// FP8 linear layers (fp8.hip): quantisers and the K = 128 MFMA GEMM
+bool fp8_gemm_supported(int64_t M, int64_t N, int64_t K) { return gk::fp8_gemm_supported(M, N, K); }
+
+gk::Fp8Src check_fp8_src(const at::Tensor& x, const char* name) {
+  check_dev(x, name);
+  TORCH_CHECK(x.dim() == 2 && (x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kFloat), name,
+              " must be a 2-D bf16 or fp32 tensor");
+  TORCH_CHECK(gk::fp8_quant_supported(x.size(0), x.size(1)) && (uintptr_t)x.data_ptr() % 16 == 0, name,
+              ": the row length must be a multiple of 16 and the storage 16-byte aligned");
+  return gk::Fp8Src{x.data_ptr(), x.size(0), x.size(1), x.scalar_type() == at::kBFloat16};
+}
+
+void check_fp8_q(const at::Tensor& q, const char* name, int64_t R, int64_t C) {
+  check_dev(q, name);
+  TORCH_CHECK(q.element_size() == 1 && q.dim() == 2 && q.size(0) == R && q.size(1) == C &&
+                  (uintptr_t)q.data_ptr() % 16 == 0, name, " must be an 8-bit [", R, ", ", C, "] tensor, 16-byte aligned");
+}
+
+void check_fp8_scale(const at::Tensor& s, const char* name) {
+  check_f32(s, name);
+  TORCH_CHECK(s.numel() == 1, name, " must hold one fp32");
+}
+
+void check_fp8_partials(const at::Tensor& p) {
+  check_dev(p, "partials");
+  TORCH_CHECK(p.scalar_type() == at::kInt && p.numel() >= gk::kFp8MaxParts, "partials must be int32[>= ",
+              gk::kFp8MaxParts, "]");
+}
+
+void fp8_amax(at::Tensor x, at::Tensor partials) {
+  const gk::Fp8Src src = check_fp8_src(x, "x");
+  check_fp8_partials(partials);
+  c10::DeviceGuard guard(x.device());
+  gk::fp8_amax(src, reinterpret_cast<uint32_t*>(partials.data_ptr<int32_t>()), cur_stream(x));
+}
+
+void fp8_quantize(at::Tensor x, at::Tensor partials, at::Tensor q, at::Tensor scale, int64_t fmt) {
+  const gk::Fp8Src src = check_fp8_src(x, "x");
+  check_fp8_partials(partials);
+  check_fp8_q(q, "q", src.R, src.C);
+  check_fp8_scale(scale, "scale");
+  TORCH_CHECK(fmt == gk::kFp8E4M3 || fmt == gk::kFp8E5M2, "fmt must be 0 (e4m3) or 1 (e5m2)");
+  c10::DeviceGuard guard(x.device());
+  gk::fp8_quantize(src, reinterpret_cast<const uint32_t*>(partials.data_ptr<int32_t>()), (int)fmt, q.data_ptr(),
+                   scale.data_ptr<float>(), cur_stream(x));
+}
+
+void fp8_quantize_t(at::Tensor w, at::Tensor partials, at::Tensor w8, at::Tensor w8t, at::Tensor scale) {
+  const gk::Fp8Src src = check_fp8_src(w, "w");
+  check_fp8_partials(partials);
+  check_fp8_q(w8, "w8", src.R, src.C);
+  check_fp8_q(w8t, "w8t", src.C, src.R);
+  check_fp8_scale(scale, "scale");
+  TORCH_CHECK(src.R < ((int64_t)1 << 30), "w has too many rows");
+  c10::DeviceGuard guard(w.device());
+  gk::fp8_quantize_t(src, reinterpret_cast<const uint32_t*>(partials.data_ptr<int32_t>()), w8.data_ptr(),
+                     w8t.data_ptr(), scale.data_ptr<float>(), cur_stream(w));
+}
+
+void fp8_gemm_nt(at::Tensor a8, at::Tensor sa, at::Tensor b8, at::Tensor sb, c10::optional<at::Tensor> bias,
+                 at::Tensor out, int64_t afmt) {
+  TORCH_CHECK(a8.dim() == 2 && b8.dim() == 2 && a8.size(1) == b8.size(1), "fp8_gemm_nt: a8 [M, K], b8 [N, K]");
+  const int64_t M = a8.size(0), K = a8.size(1), N = b8.size(0);
+  TORCH_CHECK(gk::fp8_gemm_supported(M, N, K), "fp8_gemm_nt: needs M >= 1 and N, K multiples of 128, got M ", M,
+              " N ", N, " K ", K);
+  check_fp8_q(a8, "a8", M, K);
+  check_fp8_q(b8, "b8", N, K);
+  check_fp8_scale(sa, "sa");
+  check_fp8_scale(sb, "sb");
+  TORCH_CHECK(afmt == gk::kFp8E4M3 || afmt == gk::kFp8E5M2, "afmt must be 0 (e4m3) or 1 (e5m2)");
+  check_dev(out, "out");
+  TORCH_CHECK(out.scalar_type() == at::kBFloat16 && out.dim() == 2 && out.size(0) == M && out.size(1) == N &&
+                  (uintptr_t)out.data_ptr() % 16 == 0, "out must be bf16 [M, N], 16-byte aligned");
+  const float* bp = nullptr;
+  if (bias.has_value() && bias->defined()) {
+    check_f32(*bias, "bias");
+    TORCH_CHECK(bias->numel() == N && (uintptr_t)bias->data_ptr() % 16 == 0, "bias must be fp32 [N], 16-byte aligned");
+    bp = bias->data_ptr<float>();
+  }
+  c10::DeviceGuard guard(a8.device());
+  gk::fp8_gemm_nt(gk::Fp8GemmArgs{a8.data_ptr(), sa.data_ptr<float>(), (int)afmt, b8.data_ptr(), sb.data_ptr<float>(),
+                                  bp, out.data_ptr(), M, (int)N, (int)K},
+                  cur_stream(a8));
+}
+
 // fused BERT input embedding (embed.hip)
 bool emb_supported(int64_t H, int64_t NT) { return gk::emb_supported((int)H, (int)NT); }
 int64_t emb_part_floats(int64_t H) { return (int64_t)gk::emb_type_parts() * 2 * H; }
@@ -2270,6 +2355,11 @@ TORCH_LIBRARY(gksgd, m) {
   m.def("xent_supported(int V) -> bool", &xent_supported);
   m.def("xent_forward(Tensor logits, Tensor labels, Tensor(a!) lse, Tensor(b!) loss, int ignore) -> ()");
   m.def("xent_backward(Tensor logits, Tensor labels, Tensor lse, Tensor scale, Tensor(a!) grad, int ignore) -> ()");
+  m.def("fp8_gemm_supported(int M, int N, int K) -> bool", &fp8_gemm_supported);
+  m.def("fp8_amax(Tensor x, Tensor(a!) partials) -> ()");
+  m.def("fp8_quantize(Tensor x, Tensor partials, Tensor(a!) q, Tensor(b!) scale, int fmt) -> ()");
+  m.def("fp8_quantize_t(Tensor w, Tensor partials, Tensor(a!) w8, Tensor(b!) w8t, Tensor(c!) scale) -> ()");
+  m.def("fp8_gemm_nt(Tensor a8, Tensor sa, Tensor b8, Tensor sb, Tensor? bias, Tensor(a!) out, int afmt) -> ()");
   m.def("emb_supported(int H, int NT) -> bool", &emb_supported);
   m.def("emb_part_floats(int H) -> int", &emb_part_floats);
   m.def("emb_forward(Tensor ids, Tensor? tt, Tensor Ww, Tensor Wp, Tensor Wt, Tensor(a!) out) -> ()");
@@ -2385,6 +2475,10 @@ TORCH_LIBRARY_IMPL(gksgd, CUDA, m) {
   m.impl("add_ln_forward", &add_ln_forward);
   m.impl("xent_forward", &xent_forward);
   m.impl("xent_backward", &xent_backward);
+  m.impl("fp8_amax", &fp8_amax);
+  m.impl("fp8_quantize", &fp8_quantize);
+  m.impl("fp8_quantize_t", &fp8_quantize_t);
+  m.impl("fp8_gemm_nt", &fp8_gemm_nt);
   m.impl("emb_forward", &emb_forward);
   m.impl("emb_backward", &emb_backward);
   m.impl("add_ln_backward", &add_ln_backward);

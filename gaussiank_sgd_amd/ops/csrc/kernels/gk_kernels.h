@@ -629,6 +629,27 @@ void xent_forward(const void* logits, const int64_t* labels, float* lse, float* 
 void xent_backward(const void* logits, const int64_t* labels, const float* lse, const float* scale, void* grad,
                    int64_t R, int V, int64_t ignore, hipStream_t s);
 
+// FP8 linear layers (fp8.hip): per-tensor power-of-two quantisers and the K = 128 MFMA GEMM.
+// A scale tensor is one fp32 on the device holding 2^-e (the dequantising factor).
+enum { kFp8E4M3 = 0, kFp8E5M2 = 1 };   // also the MFMA's format field
+constexpr int kFp8MaxParts = 1024;     // amax partials, one per workgroup of fp8_amax
+struct Fp8Src { const void* x; int64_t R; int64_t C; bool bf16; };   // contiguous [R, C], bf16 or fp32
+bool fp8_quant_supported(int64_t R, int64_t C);                      // C a multiple of 16
+void fp8_amax(const Fp8Src& x, uint32_t* partials, hipStream_t s);
+void fp8_quantize(const Fp8Src& x, const uint32_t* partials, int fmt, void* q, float* scale, hipStream_t s);
+// the weight [N, K] as e4m3: w8 [N, K] and w8t [K, N], one scale
+void fp8_quantize_t(const Fp8Src& w, const uint32_t* partials, void* w8, void* w8t, float* scale, hipStream_t s);
+// C (bf16 [M, N]) = (A [M, K] . B [N, K]^T) * sa * sb + bias; A: afmt, B: e4m3; bias: opt, fp32 [N]
+struct Fp8GemmArgs {
+  const void* A; const float* sa; int afmt;
+  const void* B; const float* sb;
+  const float* bias;
+  void* C;
+  int64_t M; int N; int K;
+};
+bool fp8_gemm_supported(int64_t M, int64_t N, int64_t K);   // N, K multiples of 128
+void fp8_gemm_nt(const Fp8GemmArgs& g, hipStream_t s);
+
 // Fused residual add (+ dropout) + LayerNorm over rows of H bf16 (ln.hip).
 // forward : h = x + dropout_p(a), y = LN(h) * gamma + beta; saves h (bf16),
 //           mean, rstd (fp32 per row).  The dropout mask is a hash of

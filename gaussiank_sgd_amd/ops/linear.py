@@ -24,6 +24,13 @@ keys).  fp32 inputs without autocast (the reference's precision) take the same
 path on the fp32 MFMA kernels (``v_mfma_f32_16x16x4_f32``) and the fp32 column
 pass; off the GPU it is the stock layer (+ ``F.gelu``).
 
+FP8 (opt-in: ``GKSGD_FP8_LINEAR=1`` / ``set_fp8(True)`` / ``--fp8-linear``,
+per module ``FastLinear.fp8``): on the bf16 path, layers whose in and out
+features are multiples of 128 run the forward and the grad-input GEMM on 8-bit
+operands (ops/fp8.py states the numerics: e4m3 activations and weights, e5m2
+output gradients, per-tensor power-of-two scales, fp32 accumulation); the
+grad-weight and bias-gradient kernels are the bf16 ones, unchanged.
+
 Reference parity: the reference's models use ``nn.Linear`` (models/fcn.py,
 models/lstm.py:29); BERT is not in the reference (BASELINE config 5).
 """
@@ -39,9 +46,21 @@ import torch.nn.functional as F
 
 from . import accum_grad_, load, require_native
 from . import autotune
+from . import fp8
 from . import streams
 
 _ENABLED = os.environ.get("GKSGD_FASTLINEAR", "1") != "0"
+_FP8 = os.environ.get("GKSGD_FP8_LINEAR", "0") == "1"
+
+
+def set_fp8(on: bool) -> None:
+    """The global FP8 switch (``GKSGD_FP8_LINEAR``) that modules with ``fp8 = None`` follow."""
+    global _FP8
+    _FP8 = bool(on)
+
+
+def fp8_enabled() -> bool:
+    return _FP8
 
 
 def _g():
@@ -319,7 +338,7 @@ class _LinearFn(torch.autograd.Function):
     reports the parameter ready)."""
 
     @staticmethod
-    def forward(ctx, x, weight, w_bf16, wsink, bias, bsink, gelu, b_bf16=None, dt=torch.bfloat16):
+    def forward(ctx, x, weight, w_bf16, wsink, bias, bsink, gelu, b_bf16=None, dt=torch.bfloat16, use_fp8=False):
         shape = x.shape
         K = shape[-1]
         x2 = x.reshape(-1, K)
@@ -329,11 +348,19 @@ class _LinearFn(torch.autograd.Function):
         w = w_bf16 if w_bf16 is not None else weight.detach().to(dt)
         w = w.contiguous()
         b = bias.detach().float().contiguous() if bias is not None else None
-        y = _fwd(x2, w, b, b_bf16)
+        w8t = sw = None
+        if use_fp8:
+            # 8-bit operands (ops/fp8.py); w8t and its scale serve the grad-input
+            assert dt == torch.bfloat16, "the fp8 path takes bf16 operands"
+            x8, sx = fp8.quantize(x2, "e4m3")
+            w8, w8t, sw = fp8.quantize_weight(w)
+            y = fp8.gemm_nt(x8, sx, w8, sw, b)
+        else:
+            y = _fwd(x2, w, b, b_bf16)
         pre = None
         if gelu:
             pre, y = y, F.gelu(y)
-        ctx.save_for_backward(x2, w, pre)
+        ctx.save_for_backward(x2, w, pre, w8t, sw)
         ctx.wsink, ctx.bsink, ctx.gelu = wsink, bsink, gelu
         ctx.has_bias = bias is not None
         ctx.in_shape = shape
@@ -343,7 +370,7 @@ class _LinearFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        x2, w, pre = ctx.saved_tensors
+        x2, w, pre, w8t, sw = ctx.saved_tensors
         N, K = w.shape
         dy2 = dy.reshape(-1, N)
         if dy2.dtype != x2.dtype:
@@ -362,7 +389,11 @@ class _LinearFn(torch.autograd.Function):
                 bias_grad_acc_(db, dpre)
         # one zero-padded copy of dpre for both GEMMs (K / N not multiples of 64)
         pads = {} if _PAD_SHARE else None
-        dx = _dgrad(dpre, w, pads).view(ctx.in_shape) if ctx.needs_input_grad[0] else None
+        if w8t is not None and ctx.needs_input_grad[0]:
+            d8, sd = fp8.quantize(dpre, "e5m2")
+            dx = fp8.gemm_nt(d8, sd, w8t, sw).view(ctx.in_shape)
+        else:
+            dx = _dgrad(dpre, w, pads).view(ctx.in_shape) if ctx.needs_input_grad[0] else None
         gweight = None
         if ctx.needs_input_grad[1]:
             gw = _target(ctx.wsink)
@@ -387,7 +418,7 @@ class _LinearFn(torch.autograd.Function):
                 gbias = None
             else:
                 gbias = gbias.to(ctx.bdtype)
-        return dx, gweight, None, None, gbias, None, None, None, None
+        return dx, gweight, None, None, gbias, None, None, None, None, None
 
 
 def _supported(x: torch.Tensor, mod: nn.Linear) -> bool:
@@ -399,7 +430,10 @@ class FastLinear(nn.Linear):
     """``nn.Linear`` whose bf16 training path on a GPU runs the autotuned MFMA
     kernels and the fused bias-gradient pass; ``forward(x, act="gelu")``
     applies GELU with its backward fused into that pass.  Everywhere else it
-    is the stock layer (+ ``F.gelu``)."""
+    is the stock layer (+ ``F.gelu``).  ``fp8``: True / False puts this module's
+    bf16 path on / keeps it off the 8-bit GEMMs, None follows ``set_fp8``."""
+
+    fp8: Optional[bool] = None
 
     def forward(self, x: torch.Tensor, act: Optional[str] = None) -> torch.Tensor:
         if act not in (None, "gelu"):
@@ -431,7 +465,10 @@ class FastLinear(nn.Linear):
                 wsink = None
             if not torch.is_grad_enabled() or self.bias is None or not self.bias.requires_grad:
                 bsink = None
-            return _LinearFn.apply(x, self.weight, w_bf16, wsink, self.bias, bsink, act == "gelu", b_bf16)
+            use_fp8 = (_FP8 if self.fp8 is None else self.fp8) and self.in_features % 128 == 0 and \
+                self.out_features % 128 == 0
+            return _LinearFn.apply(x, self.weight, w_bf16, wsink, self.bias, bsink, act == "gelu", b_bf16,
+                                   torch.bfloat16, use_fp8)
         slow = getattr(self, "_gk_slow", None)
         y = slow(x) if slow is not None else super().forward(x)
         return F.gelu(y) if act == "gelu" else y

@@ -242,6 +242,16 @@ def _add_optimizer_flags(p):
                    help="with --optimizer adamw: LAMB, the AdamW direction scaled per tensor by ||w|| / ||u|| "
                         "(not for the 1-D / bn / bias group), run as the fused arena update")
     p.add_argument("--trust-clip", type=float, default=None, help="upper bound of the trust ratio (default: none)")
+    p.add_argument("--fp8-linear", action="store_true",
+                   help="with --amp bf16: FastLinear forward and grad-input GEMMs on FP8 operands (ops/fp8.py; "
+                        "default: GKSGD_FP8_LINEAR, else off)")
+
+
+def apply_fp8_flag(args) -> None:
+    """--fp8-linear turns the global switch on; without it GKSGD_FP8_LINEAR stands."""
+    if args.fp8_linear:
+        from ..ops import linear
+        linear.set_fp8(True)
 
 
 class OptimizerArgumentParser(argparse.ArgumentParser):
@@ -253,6 +263,8 @@ class OptimizerArgumentParser(argparse.ArgumentParser):
             self.error("--trust-ratio needs --optimizer adamw (LAMB is AdamW plus trust ratios), not %s" % ns.optimizer)
         if ns.trust_clip is not None and not ns.trust_ratio:
             self.error("--trust-clip needs --trust-ratio (with --optimizer adamw)")
+        if getattr(ns, "fp8_linear", False) and ns.amp != "bf16":
+            self.error("--fp8-linear needs --amp bf16 (the 8-bit GEMMs replace the bf16 ones)")
         return ns
 
 
@@ -319,6 +331,7 @@ def build_parser():
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    apply_fp8_flag(args)
     hvd.init()
     nworkers = args.nworkers or hvd.size()
     batch_size = args.batch_size * args.nsteps_update

@@ -123,6 +123,8 @@ def build_parser():
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    from .dist_trainer import apply_fp8_flag
+    apply_fp8_flag(args)
     batch_size = args.batch_size * args.nsteps_update
     relative_path = os.path.join(args.logdir_root, "singlegpu-%s/%s-n%d-bs%d-lr%.4f-ns%d" % (
         settings.PREFIX, args.dnn, 1, batch_size, args.lr, args.nsteps_update))
