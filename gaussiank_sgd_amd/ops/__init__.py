@@ -11,6 +11,12 @@ Packed record layout (one per rank and bucket, int32 words)::
     [0] sent  [1] total  [2] chosen candidate  [3] threshold (fp32 bits)
     [4 : 4+k_cap]            int32 indices (ascending)
     [4+k_cap : 4+2*k_cap]    fp32 values (bit-cast)
+
+Compact record (``record16_words``; opt-in wire format, ``pack_records16_`` / ``reduce_records16_``)::
+
+    [0 : 4]                  the same header
+    [4 : 4+nseg+1]           seg_off: position of the first entry of every 65,536-element segment
+    then ceil(k_cap/2) words of 16-bit indices inside the segment, and as many of bf16 values
 """
 from __future__ import annotations
 
@@ -746,6 +752,112 @@ def apply_records_sgd_(w: torch.Tensor, w_bf16: Optional[torch.Tensor], records:
     w[idx] = w[idx] - lr_eff * (s * torch.tensor(scale, dtype=torch.float32))
     if w_bf16 is not None:
         w_bf16[idx] = w[idx].to(torch.bfloat16)
+
+
+# ---------------------------------------------------------------------------
+# compact records: 16-bit segment indices and bf16 values (records16.hip)
+# ---------------------------------------------------------------------------
+SEG_SHIFT = 16   # 65,536 elements per segment
+
+
+def record16_words(n: int, k_cap: int) -> int:
+    """int32 words of the compact record of an ``n``-element bucket::
+
+        hdr[REC_HDR] | seg_off[nseg + 1] | idx16[k_cap] (two per word) | val16[k_cap] (bf16, two per word)
+
+    ``nseg = ceil(n / 65536)``; ``seg_off[s]`` is the position of the first
+    entry with ``idx >> 16 >= s`` and ``seg_off[nseg] = min(sent, k_cap)``."""
+    nseg = max((int(n) + (1 << SEG_SHIFT) - 1) >> SEG_SHIFT, 1)
+    return REC_HDR + nseg + 1 + 2 * ((int(k_cap) + 1) // 2)
+
+
+def _halfwords(words: torch.Tensor) -> torch.Tensor:
+    """The two unsigned 16-bit halves of every int32 word (low half first), as int64."""
+    w = words.to(torch.int64) & _M32
+    return torch.stack((w & 0xFFFF, w >> 16), dim=-1).view(-1)
+
+
+def _words_of(halves: torch.Tensor) -> torch.Tensor:
+    h = halves.view(-1, 2)
+    w = h[:, 0] | (h[:, 1] << 16)
+    return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
+
+
+def unpack_record16(rec: torch.Tensor, n: int, k_cap: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(int64 indices, fp32 values) of the entries of one compact record (host tensors)."""
+    rec = rec.detach().cpu()
+    nseg = record16_words(n, 0) - REC_HDR - 1
+    half = (k_cap + 1) // 2
+    so = rec[REC_HDR:REC_HDR + nseg + 1].to(torch.int64)
+    cnt = min(max(int(so[nseg]), 0), k_cap)
+    at = REC_HDR + nseg + 1
+    lo = _halfwords(rec[at:at + half])[:cnt]
+    bits = _halfwords(rec[at + half:at + 2 * half])[:cnt] << 16
+    seg = torch.searchsorted(so[1:nseg].contiguous(), torch.arange(cnt, dtype=torch.int64), right=True)
+    val = torch.where(bits >= 2 ** 31, bits - 2 ** 32, bits).to(torch.int32).view(torch.float32)
+    return (seg << SEG_SHIFT) | lo, val
+
+
+def pack_records16_(record: torch.Tensor, k_cap: int, r: torch.Tensor, out: torch.Tensor) -> None:
+    """Pack the rank's full record of the bucket with residual ``r`` into the
+    compact record ``out`` (``record16_words(r.numel(), k_cap)`` words).  The
+    bf16 rounding residue ``val - bf16(val)`` goes to ``r[idx]`` (the slot the
+    selection cleared) and ``record``'s values are overwritten with the rounded
+    ones, so ``r + record`` is still the accumulator.  Async on GPU."""
+    k_cap, n = int(k_cap), r.numel()
+    if r.is_cuda:
+        require_native(r)
+        _ops().pack_records16(record, k_cap, r, out)
+        return
+    nseg = record16_words(n, 0) - REC_HDR - 1
+    half = (k_cap + 1) // 2
+    sent = min(max(int(record[0]), 0), k_cap)
+    idx = record[REC_HDR:REC_HDR + sent].long()
+    val = record[REC_HDR + k_cap:REC_HDR + k_cap + sent].view(torch.float32)
+    v16 = val.to(torch.bfloat16)
+    r[idx] = val - v16.float()
+    val.copy_(v16.float())
+    out[:REC_HDR] = record[:REC_HDR]
+    # seg_off[s] = #{j : idx[j] >> 16 < s}
+    out[REC_HDR:REC_HDR + nseg + 1] = torch.searchsorted(
+        (idx >> SEG_SHIFT).contiguous(), torch.arange(nseg + 1, dtype=torch.int64)).to(torch.int32)
+    out[REC_HDR + nseg] = sent
+    halves = torch.zeros(2, 2 * half, dtype=torch.int64)
+    halves[0, :sent] = idx & 0xFFFF
+    halves[1, :sent] = (val.view(torch.int32).to(torch.int64) >> 16) & 0xFFFF
+    at = REC_HDR + nseg + 1
+    out[at:at + half] = _words_of(halves[0])
+    out[at + half:at + 2 * half] = _words_of(halves[1])
+
+
+def reduce_records16_(dst: torch.Tensor, records: torch.Tensor, P: int, k_cap: int, scale: float,
+                      lr: Optional[float] = None, lr_mult: Optional[torch.Tensor] = None,
+                      w_bf16: Optional[torch.Tensor] = None) -> None:
+    """``scatter_add_records_(deterministic=True)`` over ``P`` gathered compact
+    records: every index is summed over the ranks in rank order (fp32) and
+    scaled once, ``dst[idx] += scale * sum``.  With ``lr`` it is
+    ``apply_records_sgd_`` instead: ``dst`` are the weights,
+    ``dst[idx] -= lr * lr_mult * (scale * sum)`` and ``w_bf16[idx]`` is refreshed."""
+    P, k_cap, n = int(P), int(k_cap), dst.numel()
+    if dst.is_cuda:
+        require_native(dst)
+        if lr is None:
+            _ops().reduce_records16(dst, records.contiguous(), P, k_cap, float(scale))
+        else:
+            _ops().apply_records16_sgd(dst, w_bf16, records.contiguous(), P, k_cap, float(scale), float(lr), lr_mult)
+        return
+    words = record16_words(n, k_cap)
+    full = torch.zeros(P, REC_HDR + 2 * k_cap, dtype=torch.int32)
+    for q in range(P):
+        idx, val = unpack_record16(records[q * words:(q + 1) * words], n, k_cap)
+        full[q, 0] = idx.numel()
+        full[q, REC_HDR:REC_HDR + idx.numel()] = idx.to(torch.int32)
+        full[q, REC_HDR + k_cap:REC_HDR + k_cap + idx.numel()] = val.view(torch.int32)
+    if lr is None:
+        idx, s = _rank_ordered_sum(full, P, k_cap, n)
+        dst[idx] += s * torch.tensor(scale, dtype=torch.float32)
+    else:
+        apply_records_sgd_(dst, w_bf16, full, P, k_cap, scale, lr, lr_mult)
 
 
 def arena_digest(x: torch.Tensor) -> Tuple[int, int]:

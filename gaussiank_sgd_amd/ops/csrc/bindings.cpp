@@ -199,6 +199,64 @@ void scatter_add_records(at::Tensor dst, at::Tensor records, int64_t P, int64_t 
                           (float)scale, deterministic ? 1 : 0, cur_stream(dst));
 }
 
+// compact records (records16.hip)
+int64_t record16_words(int64_t n, int64_t k_cap) {
+  TORCH_CHECK(n >= 1 && k_cap >= 0, "need n >= 1 and k_cap >= 0");
+  return gk::record16_words(n, k_cap);
+}
+
+static void check_records16(const at::Tensor& dst, const at::Tensor& records, int64_t P, int64_t k_cap) {
+  check_f32(dst, "dst");
+  check_dev(records, "records");
+  TORCH_CHECK(records.scalar_type() == at::kInt && records.is_contiguous(), "records must be contiguous int32");
+  TORCH_CHECK(dst.numel() >= 1 && dst.numel() < (int64_t)0x7fffffff && k_cap >= 1 && k_cap < (int64_t)0x7fffffff,
+              "need 1 <= n < 2^31 and 1 <= k_cap < 2^31");
+  TORCH_CHECK(P >= 1 && records.numel() >= P * gk::record16_words(dst.numel(), k_cap),
+              "records too small for P x record16_words(n, k_cap)");
+}
+
+void pack_records16(at::Tensor record, int64_t k_cap, at::Tensor resid, at::Tensor out) {
+  check_f32(resid, "resid");
+  check_dev(record, "record");
+  check_dev(out, "out");
+  TORCH_CHECK(record.scalar_type() == at::kInt && record.is_contiguous() && k_cap >= 1 &&
+                  k_cap < (int64_t)0x7fffffff && record.numel() >= gk::kRecHdr + 2 * k_cap,
+              "record: int32[4 + 2*k_cap]");
+  TORCH_CHECK(resid.numel() >= 1 && resid.numel() < (int64_t)0x7fffffff, "need 1 <= n < 2^31");
+  TORCH_CHECK(out.scalar_type() == at::kInt && out.is_contiguous() &&
+                  out.numel() >= gk::record16_words(resid.numel(), k_cap),
+              "out: int32[record16_words(n, k_cap)]");
+  c10::DeviceGuard guard(resid.device());
+  gk::pack_records16(record.data_ptr<int32_t>(), k_cap, resid.data_ptr<float>(), resid.numel(),
+                     out.data_ptr<int32_t>(), cur_stream(resid));
+}
+
+void reduce_records16(at::Tensor dst, at::Tensor records, int64_t P, int64_t k_cap, double scale) {
+  check_records16(dst, records, P, k_cap);
+  c10::DeviceGuard guard(dst.device());
+  gk::reduce_records16(dst.data_ptr<float>(), dst.numel(), records.data_ptr<int32_t>(), (int)P, k_cap, (float)scale,
+                       cur_stream(dst));
+}
+
+void apply_records16_sgd(at::Tensor w, c10::optional<at::Tensor> w_bf16, at::Tensor records, int64_t P,
+                         int64_t k_cap, double scale, double lr, c10::optional<at::Tensor> lr_mult) {
+  check_records16(w, records, P, k_cap);
+  uint16_t* sh = nullptr;
+  if (w_bf16.has_value() && w_bf16->defined()) {
+    TORCH_CHECK(w_bf16->scalar_type() == at::kBFloat16 && w_bf16->numel() == w.numel() && w_bf16->is_contiguous(),
+                "w_bf16 must be a contiguous bf16 tensor of w's size");
+    sh = reinterpret_cast<uint16_t*>(w_bf16->data_ptr());
+  }
+  const float* lm = nullptr;
+  if (lr_mult.has_value() && lr_mult->defined()) {
+    check_f32(*lr_mult, "lr_mult");
+    lm = lr_mult->data_ptr<float>();
+  }
+  c10::DeviceGuard guard(w.device());
+  gk::apply_records16_sgd(w.data_ptr<float>(), sh, w.numel(), records.data_ptr<int32_t>(), (int)P, k_cap,
+                          (float)scale, (float)lr, lm, cur_stream(w));
+}
+
 void fill_zero(at::Tensor dst) {
   check_f32(dst, "dst");
   c10::DeviceGuard guard(dst.device());
@@ -2226,6 +2284,11 @@ TORCH_LIBRARY(gksgd, m) {
   m.def("quality_workspace_bytes() -> int", &quality_workspace_bytes);
   m.def("selection_quality(Tensor r, Tensor record, int k, int k_cap, Tensor(a!) out, Tensor(b!) ws) -> ()");
   m.def("scatter_add_records(Tensor(a!) dst, Tensor records, int P, int k_cap, float scale, bool deterministic) -> ()");
+  m.def("record16_words(int n, int k_cap) -> int", &record16_words);
+  m.def("pack_records16(Tensor(a!) record, int k_cap, Tensor(b!) resid, Tensor(c!) out) -> ()");
+  m.def("reduce_records16(Tensor(a!) dst, Tensor records, int P, int k_cap, float scale) -> ()");
+  m.def("apply_records16_sgd(Tensor(a!) w, Tensor(b!)? w_bf16, Tensor records, int P, int k_cap, float scale, "
+        "float lr, Tensor? lr_mult=None) -> ()");
   m.def("fill_zero(Tensor(a!) dst) -> ()");
   m.def("sign_bucket_workspace_bytes() -> int", &sign_bucket_workspace_bytes);
   m.def("sign_bucket_compress(Tensor(a!) x, Tensor(b!) mask, Tensor(c!) means, Tensor(d!) ws) -> ()");
@@ -2423,6 +2486,9 @@ TORCH_LIBRARY_IMPL(gksgd, CUDA, m) {
   m.impl("selection_quality", &selection_quality);
   m.impl("scatter_add_records", &scatter_add_records);
   m.impl("apply_records_sgd", &apply_records_sgd);
+  m.impl("pack_records16", &pack_records16);
+  m.impl("reduce_records16", &reduce_records16);
+  m.impl("apply_records16_sgd", &apply_records16_sgd);
   m.impl("arena_digest", &arena_digest);
   m.impl("fill_zero", &fill_zero);
   m.impl("sign_bucket_compress", &sign_bucket_compress);

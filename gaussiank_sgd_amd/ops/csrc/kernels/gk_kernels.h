@@ -159,6 +159,21 @@ void scatter_add_records(float* dst, int64_t n, const int32_t* records, int P, i
 // refreshed at the same indices; lr_mult (optional device scalar) multiplies lr.
 void apply_records_sgd(float* w, uint16_t* w_bf16, int64_t n, const int32_t* records, int P, int64_t k_cap,
                        float scale, float lr, const float* lr_mult, hipStream_t stream);
+// ---------------------------------------------------------------------------
+// Compact records (records16.hip), int32 words, nseg = ceil(n / 65536):
+//   hdr[kRecHdr] | seg_off[nseg + 1] | idx16[k_cap] (two per word) | val16[k_cap] (bf16, two per word)
+// seg_off[s]: position of the first entry with idx >> 16 >= s; seg_off[nseg] = min(sent, k_cap).
+// ---------------------------------------------------------------------------
+int64_t record16_words(int64_t n, int64_t k_cap);
+// full: the rank's record {hdr | idx[k_cap] | val[k_cap]} of an n-element bucket.  Writes the compact
+// record to out, the bf16 rounding residue val - bf16(val) to resid[idx] and the rounded value back to
+// full's val[j] (residual + record stays the accumulator).
+void pack_records16(int32_t* full, int64_t k_cap, float* resid, int64_t n, int32_t* out, hipStream_t stream);
+// scatter_add_records (deterministic) / apply_records_sgd over P gathered compact records
+void reduce_records16(float* dst, int64_t n, const int32_t* records, int P, int64_t k_cap, float scale,
+                      hipStream_t stream);
+void apply_records16_sgd(float* w, uint16_t* w_bf16, int64_t n, const int32_t* records, int P, int64_t k_cap,
+                         float scale, float lr, const float* lr_mult, hipStream_t stream);
 // 16-byte digest of a flat fp32 arena (replica consistency checks):
 // out[0] = fp64 sum (bits), out[1] = order-independent 64-bit hash of the bits.
 void arena_digest(const float* x, int64_t n, uint64_t* out, uint64_t* ws, hipStream_t stream);

@@ -173,6 +173,22 @@ class _DistributedOptimizer(torch.optim.Optimizer):
         # dense aggregate (clip_grad_norm_, aggregated_grads()).
         self._sparse_apply_opt = bool(opts.get("sparse_apply", _env_flag("GKSGD_SPARSE_APPLY", True)))
         self._pending_apply = False
+        # record_format: "full" ({hdr | idx int32 | val fp32}, 8 bytes per entry) or "compact" (ops.record16_words:
+        # 16-bit segment indices and bf16 values, 4 bytes per entry; the bf16 rounding residue stays in the
+        # error-feedback residual, so it needs a fused sparse compressor that keeps one)
+        self._record_format = str(opts.get("record_format") or os.environ.get("GKSGD_RECORD_FORMAT") or "full")
+        if self._record_format not in ("full", "compact"):
+            raise ValueError("record_format must be 'full' or 'compact', not %r" % (self._record_format,))
+        self._compact = self._record_format == "compact"
+        if self._compact:
+            comp = compression
+            if not (is_sparse and density < 1 and getattr(comp, "fused", False) and not getattr(comp, "dense", False)
+                    and hasattr(comp, "k_of")):
+                raise ValueError("record_format='compact' needs a fused sparse compressor at a density below 1 "
+                                 "(the dense and sign-bucket paths exchange no records)")
+            if not getattr(comp, "ec", False):
+                raise ValueError("record_format='compact' needs a compressor that keeps an error-feedback residual "
+                                 "(%s does not): the bf16 rounding residue is stored there" % getattr(comp, "name", comp))
         self._base_cls = opts.get("base_cls", None)
         self._state_dirty = False
         # cross-rank agreement on every bucket's record size and density before
@@ -264,7 +280,8 @@ class _DistributedOptimizer(torch.optim.Optimizer):
 
     def _generate_groups_mgs(self):
         P = int(self._planner_world or size())
-        _, _, ct, ag = models_for(P, self._density, self._planner_preset)
+        _, _, ct, ag = models_for(P, self._density, self._planner_preset,
+                                  record_words=ops.record16_words if self._compact else None)
         sizes = [self._named_parameters[k].numel() for k in self._seq_layernames]
         self._sizes = sizes
         return plan_mgs(self._seq_layernames, self._layerwise_times, sizes, ct, ag)
@@ -326,7 +343,9 @@ class _DistributedOptimizer(torch.optim.Optimizer):
                 kmax = comp.k_of(b.numel, max(self.get_current_density(b.name), max_density))
                 kcap_max = comp.k_cap_for(kmax, b.numel)
                 b.bufs = ops.CompressBuffers(kcap_max, dev)
-                b.gathered = torch.zeros(P * (ops.REC_HDR + 2 * kcap_max), dtype=torch.int32, device=dev)
+                b.gathered = torch.zeros(P * self._rec_words(b, kcap_max), dtype=torch.int32, device=dev)
+                if self._compact:
+                    b.extra["rec16"] = torch.zeros(self._rec_words(b, kcap_max), dtype=torch.int32, device=dev)
                 if getattr(comp, "mode", None) == ops.MODE_RANDOMK:
                     # random-k must never pick the arena's padding slots
                     layout = [(o, self._named_parameters[k].numel()) for k, o in zip(b.keys, b.offsets)]
@@ -515,17 +534,24 @@ class _DistributedOptimizer(torch.optim.Optimizer):
         host = torch.tensor([v - (1 << 32) if v >= (1 << 31) else v for v in vals], dtype=torch.int32)
         self._seed_dev.copy_(host, non_blocking=True)
 
+    def _rec_words(self, b, k_cap: int) -> int:
+        """int32 words of bucket ``b``'s wire record at ``k_cap`` in the format in force."""
+        if self._compact:
+            return ops.record16_words(b.span, k_cap)
+        return ops.REC_HDR + 2 * k_cap
+
     def wire_bytes_per_step(self, density: Optional[float] = None) -> int:
         """Bytes one rank puts on the wire per step: the fixed-size record of
-        every sparse bucket ((4 + 2 k_cap) int32 words), the dense fp32 bucket
-        otherwise (the sign-bucket compressor: two fp32 means)."""
+        every sparse bucket ((4 + 2 k_cap) int32 words, ops.record16_words in
+        the compact format), the dense fp32 bucket otherwise (the sign-bucket
+        compressor: two fp32 means)."""
         comp = self._compression
         name = getattr(comp, "name", "none")
         total = 0
         for b in self._arena.buckets:
             d = self.get_current_density(b.name) if density is None else density
             if self._sparse and d < 1 and hasattr(comp, "k_of"):
-                total += (ops.REC_HDR + 2 * comp.k_cap_for(comp.k_of(b.numel, d), b.numel)) * 4
+                total += self._rec_words(b, comp.k_cap_for(comp.k_of(b.numel, d), b.numel)) * 4
             elif name == "bucket":
                 total += 8
             else:
@@ -573,7 +599,7 @@ class _DistributedOptimizer(torch.optim.Optimizer):
         comp = self._compression
         if self._fused_sparse and self._sparse and density < 1:
             k = comp.k_of(b.numel, density)
-            return ops.REC_HDR + 2 * min(comp.k_cap_for(k, b.numel), b.bufs.k_cap)
+            return self._rec_words(b, min(comp.k_cap_for(k, b.numel), b.bufs.k_cap))
         if getattr(comp, "name", None) == "bucket":
             return 2
         return b.numel
@@ -660,8 +686,9 @@ class _DistributedOptimizer(torch.optim.Optimizer):
 
     def _sparse_fused(self, b, g, density, t0):
         rec, k_cap = self._compress_bucket(b, g, density)
+        wire = self._pack_bucket(b, rec, k_cap)
         t1 = self._timer()
-        gathered = self._exchange_records([b], [rec], [k_cap])[0]
+        gathered = self._exchange_records([b], [wire], [k_cap])[0]
         t2 = self._timer()
         self._finish_bucket(b, g, gathered, rec, k_cap)
         t3 = self._timer()
@@ -700,13 +727,31 @@ class _DistributedOptimizer(torch.optim.Optimizer):
         rec_words = ops.REC_HDR + 2 * k_cap
         return b.bufs.record[:rec_words], k_cap
 
+    def _pack_bucket(self, b, rec, k_cap):
+        """What goes on the wire for the bucket's full record ``rec``: the record itself, or (compact
+        format) its 16-bit packing -- one launch that also leaves the bf16 rounding residue in the
+        residual slots the selection cleared and the rounded values in ``rec``."""
+        if not self._compact:
+            return rec
+        wire = b.extra["rec16"][:self._rec_words(b, k_cap)]
+        with trace.range("gk/b%d/pack16" % b.index):
+            ops.pack_records16_(rec, k_cap, b.slice(self._arena.residuals), wire)
+        return wire
+
+    def _reduce_records(self, dst, gathered, P, k_cap):
+        """dst += the rank-ordered average of the gathered records (either format)."""
+        if self._compact:
+            ops.reduce_records16_(dst, gathered, P, k_cap, 1.0 / P)
+        else:
+            ops.scatter_add_records_(dst, gathered, P, k_cap, 1.0 / P, True)
+
     def _exchange_records(self, bs, recs, k_caps):
         """All-gather the records of one or more buckets (one grouped RCCL launch)."""
         if self._world <= 1:
             return list(recs)
-        outs = [b.gathered[: self._world * (ops.REC_HDR + 2 * kc)] for b, kc in zip(bs, k_caps)]
+        outs = [b.gathered[: self._world * self._rec_words(b, kc)] for b, kc in zip(bs, k_caps)]
         if self._check_order:
-            self._check_exchange_order([(b.index, ops.REC_HDR + 2 * kc) for b, kc in zip(bs, k_caps)])
+            self._check_exchange_order([(b.index, self._rec_words(b, kc)) for b, kc in zip(bs, k_caps)])
         with trace.range("gk/allgather/%s" % ",".join("b%d" % b.index for b in bs)):
             if len(bs) == 1:
                 self._exchanger.allgather_(outs[0], recs[0])
@@ -726,7 +771,7 @@ class _DistributedOptimizer(torch.optim.Optimizer):
             # distributed_optimizer.py:468-482), so all replicas compute
             # bit-identical aggregates for any P.
             with trace.range("gk/b%d/decompress" % b.index):
-                ops.scatter_add_records_(g, gathered, max(self._world, 1), k_cap, 1.0 / max(self._world, 1), True)
+                self._reduce_records(g, gathered, max(self._world, 1), k_cap)
             b.extra["agg_done"] = True
         self._log_selected(b.bufs.record[0:2])
         if self._quality_every and self._fused_sparse and self.train_iter % self._quality_every == 0:
@@ -757,9 +802,9 @@ class _DistributedOptimizer(torch.optim.Optimizer):
             for b in bs:
                 g = b.slice(self._arena.grads)
                 rec, kc = self._compress_bucket(b, g, self.get_current_density(b.name))
-                parts.append((b, g, rec, kc))
-            outs = self._exchange_records([p[0] for p in parts], [p[2] for p in parts], [p[3] for p in parts])
-            for (b, g, rec, kc), out in zip(parts, outs):
+                parts.append((b, g, rec, kc, self._pack_bucket(b, rec, kc)))
+            outs = self._exchange_records([p[0] for p in parts], [p[4] for p in parts], [p[3] for p in parts])
+            for (b, g, rec, kc, _), out in zip(parts, outs):
                 self._finish_bucket(b, g, out, rec, kc)
             if self._comm_stream is not None:
                 for b in bs:
@@ -902,7 +947,9 @@ class _DistributedOptimizer(torch.optim.Optimizer):
         out = {m: float(np.mean([r[m] for r in rows]))
                for m in ("record_occupancy", "topk_overlap", "energy_captured", "energy_fraction")}
         sent_per_step = float(np.mean([r["sent"] for r in rows])) * len(self._arena.buckets)
-        out["compression_ratio_used"] = int(np.sum(self._sizes)) * 4.0 / (8.0 * sent_per_step) if sent_per_step else 0.0
+        per_entry = 4.0 if self._compact else 8.0    # compact records: 16-bit index + bf16 value
+        out["compression_ratio_used"] = int(np.sum(self._sizes)) * 4.0 / (per_entry * sent_per_step) \
+            if sent_per_step else 0.0
         return out
 
     def _queue_dump(self, b, r, rec, k_cap):
@@ -1028,7 +1075,7 @@ class _DistributedOptimizer(torch.optim.Optimizer):
                 agg = b.extra.get("agg")
                 if agg is not None and not b.extra.get("agg_done", False):
                     gathered, P, k_cap = agg
-                    ops.scatter_add_records_(b.slice(self._arena.grads), gathered, P, k_cap, 1.0 / P, True)
+                    self._reduce_records(b.slice(self._arena.grads), gathered, P, k_cap)
                     b.extra["agg_done"] = True
         self._pending_apply = False
 
@@ -1191,8 +1238,11 @@ class _DistributedOptimizer(torch.optim.Optimizer):
                 if agg is None or b.extra.get("agg_done", False):
                     continue
                 gathered, P, k_cap = agg
-                ops.apply_records_sgd_(b.slice(arena.weights), b.slice(shadow) if shadow is not None else None,
-                                       gathered, P, k_cap, 1.0 / P, lr, self._lr_mult)
+                w_b, sh_b = b.slice(arena.weights), b.slice(shadow) if shadow is not None else None
+                if self._compact:
+                    ops.reduce_records16_(w_b, gathered, P, k_cap, 1.0 / P, lr=lr, lr_mult=self._lr_mult, w_bf16=sh_b)
+                else:
+                    ops.apply_records_sgd_(w_b, sh_b, gathered, P, k_cap, 1.0 / P, lr, self._lr_mult)
                 b.extra["agg_done"] = True
             self._pending_apply = False
             self._mc_applied = False
@@ -1448,7 +1498,11 @@ def DistributedOptimizer(optimizer, named_parameters=None, compression=None, is_
     (N > 0: every N-th step each fused sparse bucket's record is scored
     against the exact top-k of its accumulator on device, rows from
     ``collect_selection_quality()``; default ``GKSGD_SELECTION_QUALITY_EVERY``
-    or 0 = off; steps captured into a HIP graph are not sampled).
+    or 0 = off; steps captured into a HIP graph are not sampled),
+    ``record_format`` ('full' | 'compact'; default ``GKSGD_RECORD_FORMAT`` or
+    'full'): 'compact' exchanges ``ops.record16_words`` records -- 16-bit
+    segment indices and bf16 values, 4 bytes per entry instead of 8, the
+    rounding residue kept in the error-feedback residual.
     """
     from ..compression import compressors
     if compression is None or isinstance(compression, str):

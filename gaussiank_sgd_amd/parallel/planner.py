@@ -152,8 +152,10 @@ REFERENCE_ALPHA_BETA = {
 }
 
 
-def models_for(P: int, density: float, preset: str = "mi355x"):
-    """Return (allreduce_time(bytes), alpha, compress_time(n), allgather_time(n))."""
+def models_for(P: int, density: float, preset: str = "mi355x", record_words=None):
+    """Return (allreduce_time(bytes), alpha, compress_time(n), allgather_time(n)).
+    ``record_words(n, k_cap)``: the wire record's int32 words when it is not the full format's
+    4 + 2 k_cap (the 'mi355x' all-gather model; the reference preset keeps the reference's own)."""
     if preset == "reference":
         keys = sorted(REFERENCE_ALPHA_BETA)
         k = next((x for x in keys if x >= P), keys[-1])
@@ -163,4 +165,4 @@ def models_for(P: int, density: float, preset: str = "mi355x"):
     from ..utils import perf_model
     a = perf_model.collective_ab("allreduce", max(P, 2))[0]
     return ((lambda b: perf.allreduce_perf_model_xgmi(b, P)), a, (lambda n: perf.compress_perf_model_mi355x(n)),
-            (lambda n: perf.allgather_perf_model_xgmi(n, P, density)))
+            (lambda n: perf.allgather_perf_model_xgmi(n, P, density, record_words=record_words)))

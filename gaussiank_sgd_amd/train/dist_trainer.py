@@ -42,7 +42,7 @@ def ssgd(dnn, dataset, data_dir, nworkers, lr, batch_size, nsteps_update, max_ep
          bf16_shadow=True, momentum_correction=False, k_cap_factor=None, overlap=True, dump_grad_every=None,
          metrics_dir=None, f32_matmul=None, train_samples=None, checkpoint_every=2, save_final=False,
          hip_graph=False, selection_quality_every=None, optimizer="sgd", betas=(0.9, 0.999), adam_eps=1e-8,
-         weight_decay=None, trust_ratio=False, trust_clip=None):
+         weight_decay=None, trust_ratio=False, trust_clip=None, record_format=None):
     rank = hvd.rank()
     device = "cpu"
     if torch.cuda.is_available():
@@ -106,6 +106,8 @@ def ssgd(dnn, dataset, data_dir, nworkers, lr, batch_size, nsteps_update, max_ep
 
     # --selection-quality-every N: None leaves the optimizer's default (GKSGD_SELECTION_QUALITY_EVERY, else off)
     quality_opt = {} if selection_quality_every is None else {"selection_quality_every": int(selection_quality_every)}
+    if record_format is not None:   # None leaves the optimizer's default (GKSGD_RECORD_FORMAT, else full)
+        quality_opt["record_format"] = record_format
     optimizer = hvd.DistributedOptimizer(trainer.optimizer, named_parameters=trainer.net.named_parameters(),
                                          compression=compressors[compressor], is_sparse=is_sparse, density=density,
                                          seq_layernames=seq_layernames, layerwise_times=layerwise_times,
@@ -323,6 +325,10 @@ def build_parser():
                         "device (record_occupancy, topk_overlap, energy_captured, energy_fraction and "
                         "compression_ratio_used in the metrics lines); 0 = off (default: "
                         "GKSGD_SELECTION_QUALITY_EVERY, else off)")
+    p.add_argument("--record-format", choices=("full", "compact"), default=None,
+                   help="wire record of the sparse buckets: full (int32 indices, fp32 values: 8 bytes per entry) or "
+                        "compact (16-bit segment indices, bf16 values with the rounding residue kept in the "
+                        "residual: 4 bytes per entry); default: GKSGD_RECORD_FORMAT, else full")
     _add_optimizer_flags(p)
     p.add_argument("--save-final", action="store_true",
                    help="every rank saves its checkpoint at the end of the run (resume with --pretrain)")
@@ -366,7 +372,7 @@ def main(argv=None):
                 checkpoint_every=args.checkpoint_every, save_final=args.save_final, hip_graph=args.hip_graph,
                 selection_quality_every=args.selection_quality_every, optimizer=args.optimizer,
                 betas=(args.adam_beta1, args.adam_beta2), adam_eps=args.adam_eps, weight_decay=args.weight_decay,
-                trust_ratio=args.trust_ratio, trust_clip=args.trust_clip)
+                trust_ratio=args.trust_ratio, trust_clip=args.trust_clip, record_format=args.record_format)
 
 
 if __name__ == "__main__":

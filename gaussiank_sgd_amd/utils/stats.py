@@ -143,13 +143,17 @@ def compress_perf_model_mi355x(x: float) -> float:
     return c0 + c1 * x
 
 
-def allgather_perf_model_xgmi(x: float, P: int, density: float = 0.001, kcap_factor: float = 4.0 / 3.0) -> float:
-    """All-gather of one bucket's packed record: (4 + 2 k_cap) int32 words per rank."""
+def allgather_perf_model_xgmi(x: float, P: int, density: float = 0.001, kcap_factor: float = 4.0 / 3.0,
+                              record_words=None) -> float:
+    """All-gather of one bucket's packed record: (4 + 2 k_cap) int32 words per rank, or
+    ``record_words(n, k_cap)`` of them (the compact format: ``ops.record16_words``)."""
     if x == 0 or P <= 1:
         return 0.0
     from . import perf_model
     a, b = perf_model.collective_ab("allgather", P)
     rec_bytes = (4 + 2 * kcap_factor * max(x * density, 1.0)) * 4
+    if record_words is not None:
+        rec_bytes = record_words(int(x), int(kcap_factor * max(x * density, 1.0))) * 4
     return a + b * rec_bytes
 
 
